@@ -31,7 +31,16 @@ both nets in place.  The netting partitions by chromosome side, so there is no
 data-path collective; torch.distributed (RCCL) carries the barriers and the
 max-over-ranks clock.  value = the set's netted aligned bases / step time.
 
-Also reported (rank 0):
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only that: it
+writes C5 if --tmp does not hold it yet, warms up, times the K steps and
+prints the result line.  --dump-outputs DIR also writes what the last timed
+step computed (dump_outputs below: a seeded sample of both nets' records as
+float64 .npy arrays).  Everything else is behind --full.
+
+With --full, also checked and reported (rank 0):
+  parity_full -- both nets of the last timed step against the reference's
+                 sha256 (tests/golden/fullscale/c5.json);
+  tool_stages -- the stage laps of one more, untimed run of the tool;
   c2          -- configs[1]: the same tool on C2 (hg38 chr1 x mm10, 2e5
                  chains), N = 1 only, with its reference time;
   kernel      -- the GPU rescoring call alone (gac_score_ranges_device over
@@ -92,6 +101,11 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also run every other leg and check (parity sha256, stage laps, C2, C3, "
+                        "C4, kernel legs + rooflines, scoreChain, CPU baselines)")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed step computed as DIR/<name>.npy")
     p.add_argument("--chains", type=int, default=5_000_000, help="C5 chain count")
     p.add_argument("--seed", type=int, default=1234)
     p.add_argument("--c2-chains", type=int, default=200_000)
@@ -116,7 +130,10 @@ def parse():
     p.add_argument("--gen-only", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--launch-check", action="store_true",
                    help="start the ranks, report the process group each one sees, exit")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------- launching
@@ -1186,6 +1203,67 @@ def c3_leg(args, steps):
     return res
 
 
+# ---------------------------------------------------------------- output dump
+NET_SAMPLE_LINES = 200_000  # per net: 200 k x 12 float64 = 19.2 MB
+NET_COLUMNS = ("line", "kind", "depth", "t_start", "t_size", "other_seq", "strand", "q_start",
+               "q_size", "id", "score", "ali")
+NET_KINDS = {b"net": 0, b"fill": 1, b"gap": 2}
+
+
+def net_sample(path, other_sizes, seed, k=NET_SAMPLE_LINES):
+    """A seeded sample of a .net file's lines as numbers: (rows, totals).
+    rows is float64 (lines, len(NET_COLUMNS)), in file order: the line's
+    number, its kind (0 net, 1 fill, 2 gap, 3 anything else), its depth
+    (leading blanks), then for a fill or gap tStart, tSize, the other
+    sequence's index in `other_sizes`, strand (+1 / -1), qStart, qSize and, for
+    a fill, id, score and ali (the rescored values); a net line has its size in
+    t_size; every field a line lacks is -1.  All are integers below 2^53, so
+    float64 holds them exactly.  totals = [bytes, lines] of the whole file."""
+    with open(other_sizes) as f:
+        names = {ln.split()[0].encode(): i for i, ln in enumerate(x for x in f if x.strip())}
+    buf = np.fromfile(path, np.uint8)
+    ends = np.flatnonzero(buf == 10)
+    n = len(ends)
+    pick = np.sort(np.random.default_rng(seed).choice(n, min(k, n), replace=False))
+    starts = np.where(pick > 0, ends[pick - 1] + 1, 0)
+    rows = np.full((len(pick), len(NET_COLUMNS)), -1.0)
+    rows[:, 0] = pick
+    mv = memoryview(buf)
+    for r, s, e in zip(rows, starts.tolist(), ends[pick].tolist()):
+        line = bytes(mv[s:e])
+        w = line.split()
+        r[1] = NET_KINDS.get(w[0] if w else b"", 3)
+        r[2] = len(line) - len(line.lstrip(b" "))
+        if r[1] == 0:
+            r[4] = int(w[2])
+        elif r[1] != 3:
+            r[3], r[4], r[5] = int(w[1]), int(w[2]), names.get(w[3], -1)
+            r[6], r[7], r[8] = (1 if w[4] == b"+" else -1), int(w[5]), int(w[6])
+            kv = dict(zip(w[7::2], w[8::2]))
+            for col, key in ((9, b"id"), (10, b"score"), (11, b"ali")):
+                if key in kv:
+                    r[col] = float(kv[key])
+    return rows, np.array([buf.size, n], np.float64)
+
+
+def dump_outputs(dirname, d, outs, seed):
+    """--dump-outputs: what the last timed step computed, i.e. the two nets
+    the tool wrote (`outs`: target net, query net; 2.6 GB of text at C5), as
+    DIR/t_net.npy and DIR/q_net.npy -- net_sample's rows, the same seeded
+    lines in every run with the same arguments -- and DIR/net_totals.npy, the
+    [bytes, lines] of both files.  ~39 MB at C5."""
+    os.makedirs(dirname, exist_ok=True)
+    t0 = time.time()
+    totals = []
+    for name, path, other in (("t_net", outs[0], "q.sizes"), ("q_net", outs[1], "t.sizes")):
+        rows, tot = net_sample(path, os.path.join(d, other), seed)
+        np.save(os.path.join(dirname, name + ".npy"), rows)
+        totals.append(tot)
+    np.save(os.path.join(dirname, "net_totals.npy"), np.array(totals))
+    log(f"outputs: a {NET_SAMPLE_LINES}-line sample of each net in {dirname} "
+        f"({time.time() - t0:.1f}s)")
+
+
 # ---------------------------------------------------------------- main
 def main():
     args = parse()
@@ -1212,7 +1290,7 @@ def main():
         d, info = c5_files(args)
     dist, world, rank, local, one_gpu, group = init_ranks(args)
     rdist = None
-    if world == 1 and args.sharded_scorechain:
+    if world == 1 and args.full and args.sharded_scorechain:
         # rehearsal of the N > 1 scoreChain leg: a world-1 RCCL group, made
         # before this process opens the device through libgachain (torch's
         # HIP initialisation fails after it)
@@ -1230,14 +1308,22 @@ def main():
         if dist is not None:
             dist.barrier()
 
+    # The tool each step starts is linked against libgachain.so: load it here
+    # too (the library and its ABI version checked, every exported entry point
+    # resolved), so a missing or stale build is an error at setup and not a
+    # failed first step.  Loading opens no device.
+    from genomealignmenttools_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH) or not os.path.exists(TOOL):
+        raise SystemExit(f"{_lib.LIB_PATH} or {TOOL} missing: run `make` (or "
+                         "__graft_entry__.build())")
+    abi = int(_lib.lib().gac_abi_version())
     barrier()
     if rank != 0:
         d, info = c5_files(args)  # written by rank 0 (same node)
     out_base = os.path.join(d, f"ours.r{world}")
     outs = [out_base + ".t.net", out_base + ".q.net"]
-    ch = None
     stages = pmc_f = pmc_s = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         stages = staged_run(d, out_base)  # also dumps the fills for the kernel leg
         if not (args.no_pmc or args.no_kernel):
             pmc_f = pmc_traffic(args, "fills")
@@ -1284,8 +1370,10 @@ def main():
         dev = "cpu" if one_gpu else f"cuda:{local}"
         dt, _ = reduce_time_and_work(dist, dt, 0.0, device=dev)
     step_s = dt / args.steps
+    if rank == 0 and args.dump_outputs:  # the last timed step's nets
+        dump_outputs(args.dump_outputs, d, outs, args.seed)
     parity = None
-    if rank == 0:  # (outside the timed region)
+    if rank == 0 and args.full:  # (outside the timed region)
         parity = full_parity("c5", {"in_chain_sha256": os.path.join(d, "in.chain"),
                                     "chainnet_rescore.t_net_sha256": outs[0],
                                     "chainnet_rescore.q_net_sha256": outs[1]})
@@ -1295,14 +1383,15 @@ def main():
         "value": info["netted_aligned_bases"] / step_s / 1e9,
         "unit": "Gbases/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": step_s * 1e3, "step_ms_rank0": step_ms, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "int64",
+        "scaling": "strong", "vs_baseline": None, "dtype": "int64", "full": args.full,
         "data": "synthetic (seeded C5 by gac_synth: all 455 hg38 x 66 mm10 sequences at their "
                 "real sizes, planted chains; no real genomes)",
         "config": {"workload": "chainNet -rescore end to end (bin/chainNet), C5 whole genome"
                                + ("" if world == 1 else f", chromosome sides split over {world} ranks"),
                    **info, "parallelism": f"chromosome-side shards x{world}",
                    "host_threads_per_rank": int(tool_threads.get("GAC_THREADS", host_threads())),
-                   "tool_stages": stages},
+                   "tool_stages": stages,
+                   "library": {"path": os.path.relpath(_lib.LIB_PATH, REPO), "abi_version": abi}},
         # the group as torch.distributed (RCCL) saw it: n_gpus above is its size
         "process_group": group or {"backend": None, "world_size": 1,
                                    "ranks": [{"rank": 0, "local_rank": 0, "device": "cuda:0"}]},
@@ -1312,6 +1401,20 @@ def main():
     }
     if one_gpu:
         out["rehearsal"] = "GAC_BENCH_ONE_GPU: every rank on device 0 over gloo (not a GPU curve)"
+    if args.full:
+        full_legs(args, out, d, info, out_base, dist, rdist, world, rank, local, one_gpu, barrier,
+                  step_env, pmc_f, pmc_s)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    barrier()
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_legs(args, out, d, info, out_base, dist, rdist, world, rank, local, one_gpu, barrier,
+              step_env, pmc_f, pmc_s):
+    """--full: every leg beside the headline, added to rank 0's result `out`."""
+    ch = None
     if rank == 0 and world == 1 and not args.no_c2:
         try:
             out["c2"] = c2_leg(args, args.c2_steps, 1)
@@ -1393,11 +1496,6 @@ def main():
             out["scorechain_e2e"] = scorechain_e2e_leg(d, info, 2, not args.no_cpu_baseline)
         except Exception as ex:  # reported, never fatal
             out["scorechain_e2e"] = {"error": str(ex)[:300]}
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    barrier()
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

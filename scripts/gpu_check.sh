@@ -14,8 +14,9 @@ echo "pytest rc=$rc" >> "$OUT/tests.log"
 tail -3 "$OUT/tests.log"
 # 0 = pass, 1 = a test failed; anything else (abort, fault, time limit): stop here
 [ $rc -le 1 ] || exit $rc
-timeout -k 10 900 python bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
+timeout -k 10 900 python bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
 cat "$OUT/bench.json"
+ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/$OUT/prof" -o run -- python3 "$GRAFT_REPO_ROOT/bench.py" --no-cpu-baseline --steps 10 --warmup 2 "$@" > "$GRAFT_REPO_ROOT/$OUT/prof.log" 2>&1
+timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/prof" -o run -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --steps 10 --warmup 2 "$@" > "$ROOT/$OUT/prof.log" 2>&1
 echo "prof rc=$?"

@@ -106,6 +106,54 @@ def test_full_parity_helper(tmp_path):
         assert g["info"]["seed"] in (7, 1234)
 
 
+def test_dump_outputs_net_sample(tmp_path):
+    """--dump-outputs: the nets as float64 arrays.  Every line of a small net
+    (sample size >= its lines) against the text itself, the same rows from a
+    second call, and a sample smaller than the file: seeded, in file order."""
+    import bench
+    g = os.path.join(REPO, "tests", "golden", "cleaner")
+    net = os.path.join(g, "in.net")
+    with open(net) as f:
+        text = f.read()
+    lines = text.split("\n")[:-1]
+    with open(os.path.join(g, "q.sizes")) as f:
+        qnames = [ln.split()[0] for ln in f if ln.strip()]
+    rows, tot = bench.net_sample(net, os.path.join(g, "q.sizes"), 1234)
+    assert rows.dtype == np.float64 and rows.shape == (len(lines), len(bench.NET_COLUMNS))
+    assert tot.tolist() == [len(text.encode()), len(lines)]
+    col = {c: i for i, c in enumerate(bench.NET_COLUMNS)}
+    kinds = set()
+    for k, (r, ln) in enumerate(zip(rows, lines)):
+        w = ln.split()
+        assert r[col["line"]] == k and r[col["depth"]] == len(ln) - len(ln.lstrip(" "))
+        kinds.add(w[0])
+        if w[0] == "net":
+            assert r[col["kind"]] == 0 and r[col["t_size"]] == int(w[2])
+            continue
+        assert r[col["kind"]] == {"fill": 1, "gap": 2}[w[0]]
+        want = [int(w[1]), int(w[2]), qnames.index(w[3]), 1 if w[4] == "+" else -1, int(w[5]),
+                int(w[6])]
+        assert r[col["t_start"]:col["q_size"] + 1].tolist() == want
+        if w[0] == "fill":
+            kv = dict(zip(w[7::2], w[8::2]))
+            assert [r[col[c]] for c in ("id", "score", "ali")] == [float(kv[c]) for c in
+                                                                    ("id", "score", "ali")]
+        else:
+            assert r[col["id"]:].tolist() == [-1, -1, -1]
+    assert kinds == {"net", "fill", "gap"}
+    again, _ = bench.net_sample(net, os.path.join(g, "q.sizes"), 1234)
+    assert np.array_equal(rows, again)
+    few, tot2 = bench.net_sample(net, os.path.join(g, "q.sizes"), 1234, k=50)
+    assert few.shape[0] == 50 and np.array_equal(tot, tot2)
+    idx = few[:, 0].astype(int)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(few, rows[idx])
+    # the files --dump-outputs writes
+    bench.dump_outputs(str(tmp_path / "o"), g, [net, net], 1234)
+    assert sorted(os.listdir(tmp_path / "o")) == ["net_totals.npy", "q_net.npy", "t_net.npy"]
+    assert np.array_equal(np.load(tmp_path / "o" / "t_net.npy"), rows)
+    assert np.load(tmp_path / "o" / "net_totals.npy").tolist() == [tot.tolist()] * 2
+
+
 def test_rank_tool_threads(tmp_path):
     """N > 1: each rank's tool gets the node's usable CPUs shared by its
     ranks -- also under torch.distributed.run's default OMP_NUM_THREADS=1,
