@@ -138,6 +138,23 @@ _PROTOS = {
     "gac_genome_seq_name": (C.c_char_p, [C.c_void_p, C.c_int, C.c_int32]),
     "gac_genome_decode": (
         C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_char_p]),
+    "gac_genome_want_softmask": (C.c_int, [C.c_void_p, C.c_int]),
+    "gac_genome_add_seq_masked": (
+        C.c_int,
+        [C.c_void_p, C.c_int, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p],
+    ),
+    "gac_genome_decode_case": (
+        C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_char_p]),
+    "gac_twobit_mask_runs": (
+        C.c_int, [C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_void_p,
+                  C.POINTER(C.c_int32)]),
+    "gac_chain_composition": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gac_chain_composition_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gac_antirepeat_pass": (
+        C.c_int, [C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int]),
     "gac_chains_upload": (C.c_int, [C.c_void_p, C.POINTER(ChainsetDesc), C.POINTER(C.c_void_p)]),
     "gac_chains_reupload": (C.c_int, [C.c_void_p, C.POINTER(ChainsetDesc), C.c_void_p]),
     "gac_chains_free": (None, [C.c_void_p]),

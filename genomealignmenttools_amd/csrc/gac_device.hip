@@ -89,6 +89,7 @@ hipError_t launch_text_blocks(const uint8_t *text, const TextJob *jobs, int64_t 
                               long long *out, hipStream_t s);
 hipError_t launch_text_xover(const uint8_t *text, const TextXJob *jobs, int64_t n, const M25 &m,
                              int32_t *pos, int32_t *adj, hipStream_t s);
+hipError_t launch_compose(const ComposeArgs &a, hipStream_t s);
 }  // namespace gac
 
 using namespace gac;
@@ -119,6 +120,12 @@ struct Genome {
     std::vector<int32_t> run_seq, run_lo, run_hi;
     std::vector<NPiece> npieces;    // bit0 relative to the seq start until finalize
     std::vector<int32_t> npiece_seq;
+    // soft-mask plane (opt-in, gac_genome_want_softmask): the mask runs as
+    // pieces like the N runs, and the plane itself (null: not asked for)
+    bool want_mask = false;
+    std::vector<NPiece> mpieces;
+    std::vector<int32_t> mpiece_seq;
+    uint32_t *lmask = nullptr;
     // host copy kept after finalize (raw stays): merged, sorted N runs per
     // sequence, CSR by nrun_off -- host-side base access (gac_genome_view)
     std::vector<int64_t> nrun_off{0};
@@ -409,6 +416,7 @@ static void free_genome(Genome &g) {
     if (g.tb_open) gac_twobit_close(&g.tb);
     if (g.planes) hipFree(g.planes);
     if (g.nmask) hipFree(g.nmask);
+    if (g.lmask) hipFree(g.lmask);
     if (g.d_woff) hipFree(g.d_woff);
     if (g.d_nrun) hipFree(g.d_nrun);
     g = Genome();
@@ -579,9 +587,11 @@ static Genome *side_of(gac_ctx *c, int side) {
 // by the genome) and is read straight into pinned staging at finalize.
 static int add_seq(gac_ctx *c, int side, const char *name, int32_t size, const uint8_t *packed,
                    bool copy, int32_t n_nblocks, const int32_t *n_starts,
-                   const int32_t *n_sizes) {
+                   const int32_t *n_sizes, int32_t n_mask = 0, const int32_t *m_starts = nullptr,
+                   const int32_t *m_sizes = nullptr) {
     Genome *g = side_of(c, side);
-    if (!g || !name || size < 0 || (size > 0 && !packed) || n_nblocks < 0)
+    if (!g || !name || size < 0 || (size > 0 && !packed) || n_nblocks < 0 || n_mask < 0 ||
+        (n_mask > 0 && (!m_starts || !m_sizes)))
         return gac_fail(GAC_E_ARG, "gac_genome_add_seq: bad argument");
     if (g->final) return gac_fail(GAC_E_STATE, "genome side %d already finalized", side);
     if (g->index.count(name)) return gac_fail(GAC_E_ARG, "duplicate sequence %s", name);
@@ -630,6 +640,20 @@ static int add_seq(gac_ctx *c, int side, const char *name, int32_t size, const u
             len -= piece;
         }
     }
+    // mask runs (only for a side that wants the plane): pieces as above; a
+    // run reaching past the sequence is clipped (twoBit.c:858-872 clips the
+    // runs to the fragment it lower-cases)
+    for (int32_t i = 0; g->want_mask && i < n_mask; ++i) {
+        int64_t s = m_starts[i], e = s + (int64_t)m_sizes[i];
+        if (s < 0) s = 0;
+        if (e > size) e = size;
+        while (s < e) {
+            const int32_t piece = (int32_t)(e - s < 1024 ? e - s : 1024);
+            g->mpieces.push_back(NPiece{s, piece, 0});
+            g->mpiece_seq.push_back(idx);
+            s += piece;
+        }
+    }
     return GAC_OK;
 }
 
@@ -639,6 +663,29 @@ extern "C" int gac_genome_add_seq(gac_ctx *c, int side, const char *name, int32_
     if (!c) return gac_fail(GAC_E_ARG, "NULL context");
     CTX_LOCK(c);
     return add_seq(c, side, name, size, packed, true, n_nblocks, n_starts, n_sizes);
+}
+
+extern "C" int gac_genome_add_seq_masked(gac_ctx *c, int side, const char *name, int32_t size,
+                                         const uint8_t *packed, int32_t n_nblocks,
+                                         const int32_t *n_starts, const int32_t *n_sizes,
+                                         int32_t n_mask, const int32_t *mask_starts,
+                                         const int32_t *mask_sizes) {
+    if (!c) return gac_fail(GAC_E_ARG, "NULL context");
+    CTX_LOCK(c);
+    return add_seq(c, side, name, size, packed, true, n_nblocks, n_starts, n_sizes, n_mask,
+                   mask_starts, mask_sizes);
+}
+
+extern "C" int gac_genome_want_softmask(gac_ctx *c, int side) {
+    gac_clear_error();
+    Genome *g = side_of(c, side);
+    if (!g) return gac_fail(GAC_E_ARG, "gac_genome_want_softmask: bad argument");
+    CTX_LOCK(c);
+    if (g->final || !g->names.empty())
+        return gac_fail(GAC_E_STATE, "gac_genome_want_softmask: side %d already has sequences",
+                        side);
+    g->want_mask = true;
+    return GAC_OK;
 }
 
 // Staged upload of the packed payloads to d_raw (layout: seqs[i].byte_off,
@@ -833,6 +880,8 @@ extern "C" int gac_genome_finalize(gac_ctx *c, int side) {
     if (!g) return gac_fail(GAC_E_ARG, "gac_genome_finalize: bad side");
     CTX_LOCK(c);
     if (g->final) return gac_fail(GAC_E_STATE, "genome side %d already finalized", side);
+    if (g->want_mask && g->sparse)
+        return gac_fail(GAC_E_ARG, "the sparse genome upload does not carry the soft-mask plane");
     FinLaps lap;
     lap.side = side;
     HIPCHK(hipSetDevice(c->device));
@@ -862,12 +911,16 @@ extern "C" int gac_genome_finalize(gac_ctx *c, int side) {
     // past them are set here)
     HIPCHK(hipMemsetAsync(g->planes + w, 0, (alloc_words - w) * sizeof(uint2), c->stream));
     HIPCHK(hipMemsetAsync(g->nmask + w, 0xff, (alloc_words - w) * sizeof(uint32_t), c->stream));
+    if (g->want_mask) {  // all zero, then the mask runs are OR-ed in (k_nruns)
+        HIPCHK(hipMalloc(&g->lmask, alloc_words * sizeof(uint32_t)));
+        HIPCHK(hipMemsetAsync(g->lmask, 0, alloc_words * sizeof(uint32_t), c->stream));
+    }
     if (nseq) {
         HIPCHK(hipMemcpyAsync(g->d_woff, g->woff.data(), nseq * sizeof(int64_t),
                               hipMemcpyHostToDevice, c->stream));
         uint8_t *d_raw = nullptr;
         SeqDev *d_seqs = nullptr;
-        NPiece *d_np = nullptr;
+        NPiece *d_np = nullptr, *d_mp = nullptr;
         HIPCHK(hipMalloc(&d_raw, raw_bytes + 16));
         HIPCHK(hipMalloc(&d_seqs, nseq * sizeof(SeqDev)));
         lap("allocations");
@@ -913,6 +966,15 @@ extern "C" int gac_genome_finalize(gac_ctx *c, int side) {
                                   hipMemcpyHostToDevice, c->stream));
             HIPCHK(launch_nruns(d_np, np, g->nmask, c->stream));
         }
+        const int64_t nmp = (int64_t)g->mpieces.size();
+        if (nmp) {
+            for (int64_t i = 0; i < nmp; ++i)
+                g->mpieces[i].bit0 += g->woff[g->mpiece_seq[i]] * 32;
+            HIPCHK(hipMalloc(&d_mp, nmp * sizeof(NPiece)));
+            HIPCHK(hipMemcpyAsync(d_mp, g->mpieces.data(), nmp * sizeof(NPiece),
+                                  hipMemcpyHostToDevice, c->stream));
+            HIPCHK(launch_nruns(d_mp, nmp, g->lmask, c->stream));
+        }
         HIPCHK(hipStreamSynchronize(c->stream));
         lap("relayout + N runs done");
         if (d_compact) hipFree(d_compact);
@@ -920,11 +982,14 @@ extern "C" int gac_genome_finalize(gac_ctx *c, int side) {
         hipFree(d_raw);
         hipFree(d_seqs);
         if (d_np) hipFree(d_np);
+        if (d_mp) hipFree(d_mp);
     } else {
         HIPCHK(hipStreamSynchronize(c->stream));
     }
     std::vector<NPiece>().swap(g->npieces);
     std::vector<int32_t>().swap(g->npiece_seq);
+    std::vector<NPiece>().swap(g->mpieces);
+    std::vector<int32_t>().swap(g->mpiece_seq);
     {  // global N runs (chain-level N test at chain upload)
         std::vector<longlong2> gr(g->nrun_start.size());
         for (int i = 0; i < nseq; ++i)
@@ -971,7 +1036,12 @@ extern "C" int gac_genome_load_twobit_runs(gac_ctx *c, int side, gac_twobit *tbp
     CTX_LOCK(c);
     gac_twobit tb = *tbp;
     int rc = GAC_OK;
-    std::vector<int32_t> ns, nz;
+    std::vector<int32_t> ns, nz, ms, mz;
+    const bool want_mask = side_of(c, side)->want_mask;
+    if (want_mask && run_off) {
+        gac_twobit_close(&tb);
+        return gac_fail(GAC_E_ARG, "the sparse genome upload does not carry the soft-mask plane");
+    }
     for (uint32_t i = 0; i < tb.seq_count && rc == GAC_OK; ++i) {
         if (keep && !keep[i]) continue;  // a sequence this process never scores
         const gac_twobit_seq &s = tb.seqs[i];
@@ -981,8 +1051,15 @@ extern "C" int gac_genome_load_twobit_runs(gac_ctx *c, int side, gac_twobit *tbp
             ns[k] = (int32_t)gac_twobit_u32(&tb, s.n_starts_raw + 4 * k);
             nz[k] = (int32_t)gac_twobit_u32(&tb, s.n_sizes_raw + 4 * k);
         }
+        const uint32_t mc = want_mask ? s.m_count : 0;
+        ms.resize(mc);
+        mz.resize(mc);
+        for (uint32_t k = 0; k < mc; ++k) {
+            ms[k] = (int32_t)gac_twobit_u32(&tb, s.m_starts_raw + 4 * k);
+            mz[k] = (int32_t)gac_twobit_u32(&tb, s.m_sizes_raw + 4 * k);
+        }
         rc = add_seq(c, side, s.name, (int32_t)s.size, s.packed, false, (int32_t)s.n_count,
-                     ns.data(), nz.data());
+                     ns.data(), nz.data(), (int32_t)mc, ms.data(), mz.data());
         if (rc == GAC_OK && run_off) {  // this sequence's word runs
             Genome *g = side_of(c, side);
             g->sparse = true;
@@ -3041,6 +3118,100 @@ extern "C" int gac_score_chains(gac_ctx *c, const gac_chainset *cs, uint32_t fla
     HIPCHK(hipMemcpyAsync(ali, c->d_ali, n * 4, hipMemcpyDeviceToHost, s));
     if (flags & GAC_WANT_LOCAL) HIPCHK(hipMemcpyAsync(local, c->d_l, n * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return GAC_OK;
+}
+
+// ------------------------------------------------------ match composition
+// (chainAntiRepeat; k_compose reads the set as the upload left it: no
+// scoring setup, no workspace)
+static int compose_device(gac_ctx *c, const gac_chainset *cs, int64_t *d_match, int64_t *d_rep,
+                          int64_t *d_total, hipStream_t s) {
+    if (!c->g[0].final || !c->g[1].final || !c->g[0].lmask || !c->g[1].lmask)
+        return gac_fail(GAC_E_STATE, "gac_chain_composition: both genome sides need the "
+                                     "soft-mask plane (gac_genome_want_softmask before loading)");
+    const int64_t n = cs->n_chains;
+    if (n == 0) return GAC_OK;
+    if (!d_match || !d_rep || !d_total) return gac_fail(GAC_E_ARG, "NULL buffer");
+    HIPCHK(hipMemsetAsync(d_match, 0, (size_t)n * 4 * 8, s));
+    HIPCHK(hipMemsetAsync(d_rep, 0, (size_t)n * 8, s));
+    HIPCHK(hipMemsetAsync(d_total, 0, (size_t)n * 8, s));
+    ComposeArgs a;
+    a.t_planes = c->g[0].planes;
+    a.q_planes = c->g[1].planes;
+    a.t_nmask = c->g[0].nmask;
+    a.q_nmask = c->g[1].nmask;
+    a.t_lmask = c->g[0].lmask;
+    a.q_lmask = c->g[1].lmask;
+    a.chains = cs->chains;
+    a.blk = cs->blk;
+    a.coff = cs->d_coff;
+    a.tile_c0 = cs->d_tile_c0;
+    a.n_chains = n;
+    a.n_blocks = cs->n_blocks;
+    a.ntiles = (cs->n_blocks + 63) >> 6;
+    a.match = (unsigned long long *)d_match;
+    a.rep = (unsigned long long *)d_rep;
+    a.total = (unsigned long long *)d_total;
+    HIPCHK(launch_compose(a, s));
+    return GAC_OK;
+}
+
+extern "C" int gac_chain_composition_device(gac_ctx *c, const gac_chainset *cs, int64_t *d_match,
+                                            int64_t *d_rep, int64_t *d_total, void *stream) {
+    gac_clear_error();
+    if (!c) return gac_fail(GAC_E_ARG, "NULL context");
+    if (!cs || cs->ctx != c) return gac_fail(GAC_E_ARG, "NULL or orphaned chainset");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    return compose_device(c, cs, d_match, d_rep, d_total, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int gac_chain_composition(gac_ctx *c, const gac_chainset *cs, int64_t *match,
+                                     int64_t *rep, int64_t *total) {
+    gac_clear_error();
+    if (!c) return gac_fail(GAC_E_ARG, "NULL context");
+    if (!cs || cs->ctx != c) return gac_fail(GAC_E_ARG, "NULL or orphaned chainset");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t n = cs->n_chains;
+    int64_t *d = nullptr;
+    if (n) {
+        if (!match || !rep || !total) return gac_fail(GAC_E_ARG, "NULL buffer");
+        HIPCHK(hipMalloc(&d, (size_t)n * 6 * 8));
+    }
+    hipStream_t s = c->stream;
+    int rc = compose_device(c, cs, d, d + 4 * n, d + 5 * n, s);
+    hipError_t e = hipSuccess;
+    if (rc == GAC_OK && n) {
+        e = hipMemcpyAsync(match, d, (size_t)n * 4 * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(rep, d + 4 * n, (size_t)n * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(total, d + 5 * n, (size_t)n * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (d) hipFree(d);
+    if (rc == GAC_OK && e != hipSuccess)
+        return gac_fail(GAC_E_HIP, "gac_chain_composition failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+extern "C" int gac_genome_decode_case(gac_ctx *c, int side, int32_t i, int32_t start, int32_t end,
+                                      char *out) {
+    gac_clear_error();
+    Genome *g = side_of(c, side);
+    if (!g || !g->final || i < 0 || i >= (int32_t)g->sizes.size() || start < 0 ||
+        end > g->sizes[i] || start > end || !out)
+        return gac_fail(GAC_E_ARG, "gac_genome_decode_case: bad argument");
+    if (!g->lmask) return gac_fail(GAC_E_STATE, "genome side %d has no soft-mask plane", side);
+    if (start == end) return GAC_OK;
+    int rc = gac_genome_decode(c, side, i, start, end, out);
+    if (rc != GAC_OK) return rc;
+    const int64_t w0 = g->woff[i] + start / 32, w1 = g->woff[i] + (end - 1) / 32 + 1;
+    std::vector<uint32_t> lm(w1 - w0);
+    HIPCHK(hipMemcpy(lm.data(), g->lmask + w0, lm.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int32_t p = start; p < end; ++p) {
+        const int64_t w = g->woff[i] + p / 32 - w0;
+        if (!((lm[w] >> (p & 31)) & 1u)) out[p - start] = (char)(out[p - start] - 'a' + 'A');
+    }
     return GAC_OK;
 }
 

@@ -250,4 +250,20 @@ struct M25 {  // score by text code, [q * 5 + t]; code 4 (not acgt) scores 0
     int32_t m[25];
 };
 
+// k_compose (gac_compose.hip): per-chain match composition of an uploaded
+// set.  lmask[w]: the opt-in soft-mask plane of a genome side, indexed like
+// nmask -- bit i set = base 32w+i lies in a .2bit mask run (lower case with
+// twoBitReadSeqFragExt's doMask); padding words and tail bits are 0.
+struct ComposeArgs {
+    const uint2 *t_planes, *q_planes;
+    const uint32_t *t_nmask, *q_nmask, *t_lmask, *q_lmask;
+    const DChain *chains;
+    const int4 *blk;
+    const int32_t *coff, *tile_c0;  // the chain set's compact offsets / tile chains
+    int64_t n_chains, n_blocks, ntiles;
+    unsigned long long *match;  // [n_chains][4] by code T, C, A, G (zeroed by the caller)
+    unsigned long long *rep;    // [n_chains]
+    unsigned long long *total;  // [n_chains]
+};
+
 }  // namespace gac

@@ -714,8 +714,15 @@ int gac_twobit_open_ex(const char *path, gac_twobit *tb, int populate) {
         p += 4ull * s->n_count;
         s->n_sizes_raw = d + p;
         p += 4ull * s->n_count;
-        uint32_t mc = gac_twobit_u32(tb, d + p);
-        p += 4 + 8ull * mc;
+        /* soft-mask runs (twoBit.c:835-874 lower-cases them with doMask) */
+        s->m_count = gac_twobit_u32(tb, d + p);
+        p += 4;
+        if (p + 8ull * s->m_count + 4 > sz)
+            goto trunc;
+        s->m_starts_raw = d + p;
+        p += 4ull * s->m_count;
+        s->m_sizes_raw = d + p;
+        p += 4ull * s->m_count;
         p += 4; /* reserved */
         if (p + ((size_t)s->size + 3) / 4 > sz)
             goto trunc;

@@ -44,6 +44,8 @@ typedef struct gac_twobit_seq {
     uint32_t n_count;
     const uint8_t *n_starts_raw, *n_sizes_raw; /* file order, maybe byte-swapped */
     const uint8_t *packed;                     /* (size+3)/4 bytes */
+    uint32_t m_count;                          /* soft-mask runs, as the N runs */
+    const uint8_t *m_starts_raw, *m_sizes_raw;
 } gac_twobit_seq;
 
 typedef struct gac_twobit {

@@ -169,6 +169,9 @@ static void *twobit_pre_thread(void *arg) {
     return NULL;
 }
 
+static int (*g_open_hook)(gac_ctx *); /* gt_device_on_open */
+void gt_device_on_open(int (*fn)(gac_ctx *)) { g_open_hook = fn; }
+
 static void *device_thread(void *arg) {
     gt_device *d = arg;
     const double t0 = now_s();
@@ -184,6 +187,8 @@ static void *device_thread(void *arg) {
     d->open_s = now_s() - t0;
     if (rc == GAC_OK && d->mat)
         rc = gac_set_scoring(d->ctx, d->mat, d->gap);
+    if (rc == GAC_OK && g_open_hook) /* e.g. chainAntiRepeat asks for the soft-mask planes */
+        rc = g_open_hook(d->ctx);
     if (pre_ok)
         pthread_join(pre, NULL);
     for (int k = 0; k < 2; ++k) {

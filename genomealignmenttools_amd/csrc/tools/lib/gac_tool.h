@@ -91,6 +91,9 @@ void gt_device_start_keep(gt_device *d, const char *t2bit, const char *q2bit,
  * everything; an abort before they are built releases it) */
 void gt_device_start_ex(gt_device *d, const char *t2bit, const char *q2bit, const int32_t mat[16],
                         const gac_gapcalc *gap, const struct gt_names *tkeep, gt_runs *runs);
+/* before gt_device_start: fn runs on the device thread right after gac_open,
+ * before the genomes are loaded (a GAC_* code; not GAC_OK fails the bring-up) */
+void gt_device_on_open(int (*fn)(gac_ctx *));
 /* main thread only */
 gac_ctx *gt_device_join(gt_device *d);
 /* the same wait without the abort: NULL if the bring-up failed.  Safe from

@@ -9,6 +9,9 @@ twoBitOpen + twoBitReadSeqFrag (twoBit.c)    Engine.load_2bit(side, path)
 chainRead loop (chain.c:337)                 chainfile.read_chains -> Engine.upload_chains
 chainSubsetOnT + chainCalcScore (+ local)    Engine.score_ranges(chainset, ranges)
 scoreChain getChainScore (scoreChain.c:207)  Engine.score_chains(chainset) (gac_score_chains)
+twoBitReadSeqFragExt(doMask) (twoBit.c:835)  Engine.load_2bit(..., soft_mask=True), decode_case
+chainAntiRepeat's two filters' counts        Engine.chain_composition(chainset)
+  (chainAntiRepeat.c:40-117) and decision    antirepeat_pass(score, match, rep, total, minScore)
 
 Every scoring call runs on the GPU through libgachain; there is no CPU path.
 """
@@ -129,18 +132,55 @@ class Engine:
         self._gap = gap
 
     # ---- genomes
-    def load_2bit(self, side: int, path: str) -> None:
+    def load_2bit(self, side: int, path: str, soft_mask: bool = False) -> None:
+        """soft_mask: also keep the file's mask runs as the soft-mask plane
+        (chain_composition, decode_case); off, the load is unchanged."""
+        if soft_mask:
+            check(lib().gac_genome_want_softmask(self.h, side))
         check(lib().gac_genome_load_2bit(self.h, side, path.encode()))
 
-    def add_sequences(self, side: int, seqs: Iterable) -> None:
-        """seqs: iterable of (name, size, packed uint8 .2bit payload, n_starts, n_sizes)."""
-        for name, size, packed, ns, nz in seqs:
+    def add_sequences(self, side: int, seqs: Iterable, mask_runs=None) -> None:
+        """seqs: iterable of (name, size, packed uint8 .2bit payload, n_starts, n_sizes).
+        mask_runs: per sequence (starts, sizes) of its soft-mask runs (e.g.
+        synth.Genome.mruns): the side is loaded with the soft-mask plane."""
+        if mask_runs is not None:
+            check(lib().gac_genome_want_softmask(self.h, side))
+        for i, (name, size, packed, ns, nz) in enumerate(seqs):
             packed = np.ascontiguousarray(packed, dtype=np.uint8)
             ns = np.ascontiguousarray(ns, dtype=np.int32)
             nz = np.ascontiguousarray(nz, dtype=np.int32)
-            check(lib().gac_genome_add_seq(self.h, side, name.encode(), int(size), _p(packed),
-                                           len(ns), _p(ns), _p(nz)))
+            if mask_runs is None:
+                check(lib().gac_genome_add_seq(self.h, side, name.encode(), int(size),
+                                               _p(packed), len(ns), _p(ns), _p(nz)))
+                continue
+            ms = np.ascontiguousarray(mask_runs[i][0], dtype=np.int32)
+            mz = np.ascontiguousarray(mask_runs[i][1], dtype=np.int32)
+            check(lib().gac_genome_add_seq_masked(self.h, side, name.encode(), int(size),
+                                                  _p(packed), len(ns), _p(ns), _p(nz),
+                                                  len(ms), _p(ms), _p(mz)))
         check(lib().gac_genome_finalize(self.h, side))
+
+    def decode_case(self, side: int, idx: int, start: int, end: int) -> str:
+        """'ACGTN' / 'acgtn' inside mask runs, as twoBitReadSeqFragExt(doMask=TRUE)."""
+        buf = C.create_string_buffer(max(end - start, 1))
+        check(lib().gac_genome_decode_case(self.h, side, idx, start, end, buf))
+        return buf.raw[: end - start].decode()
+
+    def chain_composition(self, cs: "ChainSet"):
+        """chainAntiRepeat's counts of every chain of the set (gac_chain_composition):
+        (match int64 [n, 4] by code T, C, A, G; rep int64 [n]; total int64 [n])."""
+        n = cs.n_chains
+        match = np.zeros((n, 4), np.int64)
+        rep = np.zeros(n, np.int64)
+        total = np.zeros(n, np.int64)
+        check(lib().gac_chain_composition(self.h, cs.handle, _p(match), _p(rep), _p(total)))
+        return match, rep, total
+
+    def chain_composition_device(self, cs: "ChainSet", d_match: int, d_rep: int, d_total: int,
+                                 stream: int = 0) -> None:
+        check(lib().gac_chain_composition_device(
+            self.h, cs.handle, C.c_void_p(d_match), C.c_void_p(d_rep), C.c_void_p(d_total),
+            C.c_void_p(stream) if stream else None))
 
     def seq_index(self, side: int, name: str) -> int:
         return lib().gac_genome_seq_index(self.h, side, name.encode())
@@ -310,4 +350,24 @@ class Engine:
         return ms.value, n.value
 
 
-__all__ = ["Engine", "ChainSet", "GapCosts", "read_score_scheme", "GAC_T", "GAC_Q"]
+def antirepeat_pass(score: float, match, rep: int, total: int, min_score: int = 5000) -> bool:
+    """chainAntiRepeat's keep/drop decision for one chain from its composition
+    (gac_antirepeat_pass: degeneracyFilter then repeatFilter; host only)."""
+    m = (C.c_int64 * 4)(*[int(x) for x in match])
+    return bool(lib().gac_antirepeat_pass(float(score), m, int(rep), int(total), int(min_score)))
+
+
+def twobit_mask_runs(path: str, name: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(starts, sizes) int32 of the soft-mask runs of one sequence of a .2bit
+    file, as the host reader keeps them (gac_twobit_mask_runs)."""
+    n = C.c_int32()
+    check(lib().gac_twobit_mask_runs(path.encode(), name.encode(), 0, None, None, C.byref(n)))
+    st = np.zeros(n.value, np.int32)
+    sz = np.zeros(n.value, np.int32)
+    check(lib().gac_twobit_mask_runs(path.encode(), name.encode(), n.value, _p(st), _p(sz),
+                                     C.byref(n)))
+    return st, sz
+
+
+__all__ = ["Engine", "ChainSet", "GapCosts", "read_score_scheme", "GAC_T", "GAC_Q",
+           "antirepeat_pass", "twobit_mask_runs"]

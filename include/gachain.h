@@ -169,6 +169,34 @@ const char *gac_genome_seq_name(gac_ctx *ctx, int side, int32_t index);
 int gac_genome_decode(gac_ctx *ctx, int side, int32_t index, int32_t start,
                       int32_t end, char *out);
 
+/* ---- soft-mask plane (opt-in; chainAntiRepeat) ---------------------------
+ * The reference reads sequence with twoBitReadSeqFragExt(doMask=TRUE)
+ * (kent/src/lib/twoBit.c:835-874): everything upper case, then the .2bit
+ * mask runs lower-cased, an N inside a run included.  A side asked for the
+ * plane keeps a third bit plane beside planes/nmask: lmask[w], bit i set when
+ * base 32w+i lies in a mask run (padding and tail bits 0).  Call before
+ * gac_genome_load_2bit / gac_genome_add_seq of that side; without it a side
+ * allocates and uploads exactly what it did before.  The sparse word-run
+ * upload (chainNet -rescore's) does not carry the plane: GAC_E_ARG. */
+int gac_genome_want_softmask(gac_ctx *ctx, int side);
+/* gac_genome_add_seq with the sequence's mask runs (twoBit.c:854-872; ignored
+ * unless the side wants the plane). */
+int gac_genome_add_seq_masked(gac_ctx *ctx, int side, const char *name, int32_t size,
+                              const uint8_t *packed, int32_t n_nblocks,
+                              const int32_t *n_starts, const int32_t *n_sizes,
+                              int32_t n_mask, const int32_t *mask_starts,
+                              const int32_t *mask_sizes);
+/* [start, end) of a resident sequence as twoBitReadSeqFragExt(doMask=TRUE)
+ * returns it (twoBit.c:835-874): 'ACGTN', 'acgtn' inside mask runs (test
+ * aid).  GAC_E_STATE without the plane. */
+int gac_genome_decode_case(gac_ctx *ctx, int side, int32_t index, int32_t start,
+                           int32_t end, char *out);
+/* The mask runs of sequence `name` of a .2bit file as the host reader keeps
+ * them (file order): *count = their number, the first min(cap, *count) written
+ * to starts/sizes.  No device needed. */
+int gac_twobit_mask_runs(const char *path, const char *name, int32_t cap, int32_t *starts,
+                         int32_t *sizes, int32_t *count);
+
 /* ---- chains ------------------------------------------------------------- */
 /* At most 2^31 - 17 blocks per chain set (GAC_E_ARG beyond: upload in parts). */
 int gac_chains_upload(gac_ctx *ctx, const gac_chainset_desc *d, gac_chainset **out);
@@ -242,6 +270,32 @@ int gac_score_chains(gac_ctx *ctx, const gac_chainset *cs, uint32_t flags, int64
  * enqueued. */
 int gac_score_chains_device(gac_ctx *ctx, const gac_chainset *cs, uint32_t flags,
                             int64_t *d_global, int64_t *d_local, int32_t *d_ali, void *stream);
+
+/* ---- match composition (chainAntiRepeat) ---------------------------------
+ * For every chain c of the set, over all aligned positions of its blocks
+ * (query on the chain's strand, case travelling with the base;
+ * kent/src/hg/mouseStuff/chainAntiRepeat/chainAntiRepeat.c:143-155):
+ *   match[c*4 + b] = positions where query and target hold the same
+ *                    nucleotide b, by .2bit code T=0 C=1 A=2 G=3 (ntVal;
+ *                    degeneracyFilter's counts[], :53-66; N matches nothing)
+ *   rep[c]         = positions lower-case (in a mask run) on either side
+ *                    (repeatFilter's repCount, :102-112)
+ *   total[c]       = sum of the block sizes (:113)
+ * Exact integers.  Both sides need the soft-mask plane (GAC_E_STATE); a NULL
+ * or orphaned set is GAC_E_ARG; an empty set writes nothing.  No scoring
+ * setup is needed.  Host buffers, synchronous. */
+int gac_chain_composition(gac_ctx *ctx, const gac_chainset *cs, int64_t *match, int64_t *rep,
+                          int64_t *total);
+/* The same into device buffers on `stream` (NULL: the context's); returns
+ * once enqueued. */
+int gac_chain_composition_device(gac_ctx *ctx, const gac_chainset *cs, int64_t *d_match,
+                                 int64_t *d_rep, int64_t *d_total, void *stream);
+/* chainAntiRepeat's decision for one chain from its composition:
+ * degeneracyFilter (chainAntiRepeat.c:40-92) then repeatFilter (:94-117), in
+ * the reference's operation order in double -- a chain without a match
+ * (0/0 = NaN) is dropped as there.  1 = keep, 0 = drop.  Host only. */
+int gac_antirepeat_pass(double score, const int64_t match[4], int64_t rep, int64_t total,
+                        int min_score);
 
 /* ---- caller text (the kent in-process API's char* entry points) ---------
  * chainScoreBlock / axtScoreUngapped (kent/src/lib/chainConnect.c:14-22,
