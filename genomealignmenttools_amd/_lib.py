@@ -223,6 +223,15 @@ _PROTOS = {
         C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 14),
     "gac_crossovers": (
         C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 10),
+    "gac_chain_dp_blocks": (
+        C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 +
+        [C.c_int, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "gac_score_text_blocks": (
+        C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.POINTER(C.c_int32), C.c_void_p]),
+    "gac_text_crossovers": (
+        C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "gac_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "gac_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gac_memcpy_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),

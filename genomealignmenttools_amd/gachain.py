@@ -12,6 +12,9 @@ scoreChain getChainScore (scoreChain.c:207)  Engine.score_chains(chainset) (gac_
 twoBitReadSeqFragExt(doMask) (twoBit.c:835)  Engine.load_2bit(..., soft_mask=True), decode_case
 chainAntiRepeat's two filters' counts        Engine.chain_composition(chainset)
   (chainAntiRepeat.c:40-117) and decision    antirepeat_pass(score, match, rep, total, minScore)
+axtScoreUngapped per block (axt.c:186-194)   Engine.score_blocks / score_text_blocks (caller text)
+cBlockFindCrossover (chainConnect.c:61-105)  Engine.crossovers / text_crossovers (caller text)
+chainBlocks' kd-tree DP (chainBlock.c:400)   Engine.chain_dp_blocks (total, predecessor per block)
 
 Every scoring call runs on the GPU through libgachain; there is no CPU path.
 """
@@ -299,6 +302,83 @@ class Engine:
             self.h, cs.handle, GAC_WANT_LOCAL if want_local else 0, C.c_void_p(d_g),
             C.c_void_p(d_l) if d_l else None, C.c_void_p(d_ali),
             C.c_void_p(stream) if stream else None))
+
+    # ---- axtChain primitives
+    def score_blocks(self, t_seq, q_seq, q_strand, blk_off, blk_t, blk_q, blk_size) -> np.ndarray:
+        """axtScoreUngapped of every block (gac_score_blocks): int32 per block;
+        pair p holds blocks [blk_off[p], blk_off[p+1])."""
+        d, arrs = self._desc(t_seq, q_seq, q_strand, blk_off, blk_t, blk_q, blk_size)
+        score = np.zeros(d.n_blocks, np.int32)
+        check(lib().gac_score_blocks(self.h, d.n_chains, d.t_seq, d.q_seq, d.q_strand, d.blk_off,
+                                     d.blk_t, d.blk_q, d.blk_size, _p(score)))
+        return score
+
+    def crossovers(self, t_seq, q_seq, q_strand, lqe, lte, rqs, rts, overlap):
+        """cBlockFindCrossover of n overlaps in genome coordinates
+        (gac_crossovers): (pos int32, adj int32)."""
+        a = [np.ascontiguousarray(t_seq, np.int32), np.ascontiguousarray(q_seq, np.int32),
+             np.ascontiguousarray(q_strand, np.uint8)] + \
+            [np.ascontiguousarray(x, np.int32) for x in (lqe, lte, rqs, rts, overlap)]
+        n = len(a[0])
+        pos = np.zeros(n, np.int32)
+        adj = np.zeros(n, np.int32)
+        check(lib().gac_crossovers(self.h, n, *[_p(x) for x in a], _p(pos), _p(adj)))
+        return pos, adj
+
+    @staticmethod
+    def _texts(strs):
+        """(char*[n] array, the bytes objects it points into: keep them alive)"""
+        keep = [bytes(s) for s in strs]
+        arr = (C.c_char_p * max(len(keep), 1))(*keep)
+        return arr, keep
+
+    def score_text_blocks(self, q, t, mat) -> np.ndarray:
+        """chainScoreBlock of n blocks of caller text (gac_score_text_blocks):
+        q[i], t[i] bytes of equal length; int64 per block."""
+        n = len(q)
+        size = np.array([len(x) for x in q], np.int32)
+        assert all(len(a) == len(b) for a, b in zip(q, t))
+        qa, k1 = self._texts(q)
+        ta, k2 = self._texts(t)
+        m = np.ascontiguousarray(np.asarray(mat, np.int32).reshape(16))
+        score = np.zeros(n, np.int64)
+        check(lib().gac_score_text_blocks(self.h, n, qa, ta, _p(size),
+                                          m.ctypes.data_as(C.POINTER(C.c_int32)), _p(score)))
+        return score
+
+    def text_crossovers(self, lq, lt, rq, rt, mat):
+        """cBlockFindCrossover of n overlaps on caller text (gac_text_crossovers):
+        four bytes objects of equal length per overlap; (pos int32, adj int32)."""
+        n = len(lq)
+        ov = np.array([len(x) for x in lq], np.int32)
+        assert all(len(a) == len(b) == len(c) == len(d) for a, b, c, d in zip(lq, lt, rq, rt))
+        ptrs = [self._texts(x) for x in (lq, lt, rq, rt)]
+        m = np.ascontiguousarray(np.asarray(mat, np.int32).reshape(16))
+        pos = np.zeros(n, np.int32)
+        adj = np.zeros(n, np.int32)
+        check(lib().gac_text_crossovers(self.h, n, *[p[0] for p in ptrs], _p(ov),
+                                        m.ctypes.data_as(C.POINTER(C.c_int32)), _p(pos), _p(adj)))
+        return pos, adj
+
+    def chain_dp_blocks(self, t_seq, q_seq, q_strand, blk_off, box, score, fast: int = 1,
+                        lin_k: int = 0, min_entry: int = 0, ov_cap: int = 1024):
+        """chainBlocks' kd-tree DP of n pairs from their blocks
+        (gac_chain_dp_blocks): box int32 [n_blocks, 4] = {qStart, qEnd, tStart,
+        tEnd}.  Returns (leaf_off int64 [n + 1], tord int32 [leaves], total int64
+        [n_blocks], pred int32 [n_blocks])."""
+        a = [np.ascontiguousarray(t_seq, np.int32), np.ascontiguousarray(q_seq, np.int32),
+             np.ascontiguousarray(q_strand, np.uint8), np.ascontiguousarray(blk_off, np.int64),
+             np.ascontiguousarray(np.asarray(box, np.int32).reshape(-1, 4)),
+             np.ascontiguousarray(score, np.int32)]
+        n, nb = len(a[0]), len(a[5])
+        leaf_off = np.zeros(n + 1, np.int64)
+        tord = np.full(max(nb, 1), -1, np.int32)
+        total = np.zeros(nb, np.int64)
+        pred = np.full(nb, -2, np.int32)
+        check(lib().gac_chain_dp_blocks(self.h, n, *[_p(x) for x in a], int(fast), int(lin_k),
+                                        int(min_entry), int(ov_cap), _p(leaf_off), _p(tord),
+                                        _p(total), _p(pred)))
+        return leaf_off, tord[:int(leaf_off[-1])], total, pred
 
     # ---- device buffers / timing (bench)
     def dev_alloc(self, nbytes: int) -> int:
