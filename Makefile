@@ -21,7 +21,7 @@ CFLAGS   := -O2 -mpopcnt -std=gnu11 -fPIC -Wall -ffp-contract=off -Iinclude -I$(
 
 HOST_SRC := $(wildcard $(CSRC)/host/*.c)
 HOST_OBJ := $(patsubst $(CSRC)/host/%.c,$(OBJDIR)/host/%.o,$(HOST_SRC))
-HIP_SRC  := $(CSRC)/gac_kernels.hip $(CSRC)/gac_compose.hip $(CSRC)/gac_dp.hip $(CSRC)/gac_dptree.hip $(CSRC)/gac_device.hip $(CSRC)/gac_comm.hip
+HIP_SRC  := $(CSRC)/gac_kernels.hip $(CSRC)/gac_compose.hip $(CSRC)/gac_axtout.hip $(CSRC)/gac_dp.hip $(CSRC)/gac_dptree.hip $(CSRC)/gac_device.hip $(CSRC)/gac_comm.hip
 HIP_OBJ  := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 HDRS     := include/gachain.h $(CSRC)/gac_kernels.h $(CSRC)/gac_dp.h $(wildcard $(CSRC)/host/*.h)
 
@@ -33,7 +33,7 @@ EXECDIR  := $(PKG)/libexec
 # GB/s for the genome uploads on the box, profiles/r02f_*), and execs it --
 # before anything touches the GPU.  Either can be overridden from outside.
 # NetFilterNonNested.perl, chainSort and chainMergeSort are host-only: in bin/.
-GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat
+GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt
 HOST_TOOLS := NetFilterNonNested.perl chainSort chainMergeSort
 TOOLS    := $(addprefix $(EXECDIR)/,$(GPU_TOOLS)) $(addprefix $(BINDIR)/,$(GPU_TOOLS)) \
             $(addprefix $(BINDIR)/,$(HOST_TOOLS))

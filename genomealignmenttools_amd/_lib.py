@@ -155,6 +155,26 @@ _PROTOS = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gac_antirepeat_pass": (
         C.c_int, [C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int]),
+    "gac_abi_minor": (C.c_int, []),
+    "gac_axt_split": (
+        C.c_int, [C.POINTER(ChainsetDesc), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "gac_axt_free": (None, [C.c_void_p]),
+    "gac_axt_measure": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p]),
+    "gac_axt_measure_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p]),
+    "gac_axt_render": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "gac_axt_render_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                  C.c_void_p]),
+    "gac_axt_job_open": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]),
+    "gac_axt_job_submit": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "gac_axt_job_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "gac_axt_job_close": (None, [C.c_void_p]),
     "gac_chains_upload": (C.c_int, [C.c_void_p, C.POINTER(ChainsetDesc), C.POINTER(C.c_void_p)]),
     "gac_chains_reupload": (C.c_int, [C.c_void_p, C.POINTER(ChainsetDesc), C.c_void_p]),
     "gac_chains_free": (None, [C.c_void_p]),

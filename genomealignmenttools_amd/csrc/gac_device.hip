@@ -90,6 +90,10 @@ hipError_t launch_text_blocks(const uint8_t *text, const TextJob *jobs, int64_t 
 hipError_t launch_text_xover(const uint8_t *text, const TextXJob *jobs, int64_t n, const M25 &m,
                              int32_t *pos, int32_t *adj, hipStream_t s);
 hipError_t launch_compose(const ComposeArgs &a, hipStream_t s);
+hipError_t launch_axt_plan(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_stat(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_place(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_render(const AxtArgs &a, hipStream_t s);
 }  // namespace gac
 
 using namespace gac;
@@ -257,9 +261,14 @@ struct gac_ctx {
     // context (a kent-shim cache, a garbage-collected binding) is only deleted
     std::vector<gac_chainset *> sets;
     SmallServer srv;
+    // gac_axt_measure / gac_axt_render: the host entry points' workspace and
+    // the render jobs still open (orphaned by gac_close like the sets)
+    struct AxtWs *axt = nullptr;
+    std::vector<struct gac_axt_job *> axt_jobs;
 };
 
 static void srv_park(gac_ctx *c);
+static void axt_release(gac_ctx *c);
 
 struct CtxLock {
     std::lock_guard<std::recursive_mutex> g;
@@ -458,6 +467,7 @@ extern "C" void gac_close(gac_ctx *c) {
         }
         c->sets.clear();
     }
+    axt_release(c);
     free_genome(c->g[0]);
     free_genome(c->g[1]);
     void *bufs[] = {c->d_small,  c->d_gap_tab, c->rdesc,    c->nblk,     c->goff, c->pb0, c->agg, c->plan_off, c->lbflag, c->gflat,
@@ -3213,6 +3223,364 @@ extern "C" int gac_genome_decode_case(gac_ctx *c, int side, int32_t i, int32_t s
         if (!((lm[w] >> (p & 31)) & 1u)) out[p - start] = (char)(out[p - start] - 'a' + 'A');
     }
     return GAC_OK;
+}
+
+// ------------------------------------------------------ alignment text
+// (chainToAxt; gac_axtout.hip).  A call runs in two steps with one host wait
+// between them: the pieces are checked and counted (k_axt_plan + scan), then
+// the kernels sized by the virtual block count run.  Workspace: two grow-only
+// arenas per AxtWs (the context's for the host entry points, one per job).
+struct AxtArena {
+    char *p = nullptr;
+    size_t cap = 0;
+};
+
+struct AxtWs {
+    AxtArena a1, a2, text;
+    int64_t *h = nullptr;  // pinned: [0] V, [1] status
+};
+
+static hipError_t arena_need(AxtArena &A, size_t bytes, hipStream_t s) {
+    if (bytes <= A.cap) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(s);  // (work in flight may still use the old one)
+    if (e != hipSuccess) return e;
+    if (A.p) hipFree(A.p);
+    A.p = nullptr;
+    A.cap = 0;
+    const size_t cap = bytes + bytes / 4 + 4096;
+    e = hipMalloc((void **)&A.p, cap);
+    if (e == hipSuccess) A.cap = cap;
+    return e;
+}
+
+static void ws_free(AxtWs &w) {
+    for (AxtArena *A : {&w.a1, &w.a2, &w.text}) {
+        if (A->p) hipFree(A->p);
+        A->p = nullptr;
+        A->cap = 0;
+    }
+    if (w.h) hipHostFree(w.h);
+    w.h = nullptr;
+}
+
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// Step one.  pieces: in host memory (copied) or already on the device.  On
+// return a holds the genome, set and plan fields and a.V; status is zero.
+static int axt_plan(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_window *h_pieces,
+                    const gac_window *d_pieces, int64_t n, hipStream_t s, AxtArgs &a) {
+    if (!c->g[0].final || !c->g[1].final || !c->g[0].lmask || !c->g[1].lmask)
+        return gac_fail(GAC_E_STATE, "gac_axt: both genome sides need the soft-mask plane "
+                                     "(gac_genome_want_softmask before loading)");
+    if (n < 0 || n >= INT32_MAX) return gac_fail(GAC_E_ARG, "gac_axt: bad piece count");
+    if (!h_pieces && !d_pieces) return gac_fail(GAC_E_ARG, "NULL buffer");
+    if (!ws.h) HIPCHK(hipHostMalloc((void **)&ws.h, 64, hipHostMallocDefault));
+    const size_t b_pieces = h_pieces ? up16((size_t)n * sizeof(Window)) : 0;
+    const size_t b_pboff = up16((size_t)(n + 1) * 8), b_part = up16((size_t)(n / 2048 + 2) * 8);
+    HIPCHK(arena_need(ws.a1, b_pieces + b_pboff + b_part + 16, s));
+    char *p = ws.a1.p;
+    memset(&a, 0, sizeof(a));
+    a.t_planes = c->g[0].planes;
+    a.q_planes = c->g[1].planes;
+    a.t_nmask = c->g[0].nmask;
+    a.q_nmask = c->g[1].nmask;
+    a.t_lmask = c->g[0].lmask;
+    a.q_lmask = c->g[1].lmask;
+    a.chains = cs->chains;
+    a.blk = cs->blk;
+    a.n_chains = cs->n_chains;
+    a.n = n;
+    if (h_pieces) {
+        HIPCHK(hipMemcpyAsync(p, h_pieces, (size_t)n * sizeof(Window), hipMemcpyHostToDevice, s));
+        a.pieces = (const Window *)p;
+        p += b_pieces;
+    } else {
+        a.pieces = (const Window *)d_pieces;
+    }
+    a.pboff = (int64_t *)p;
+    p += b_pboff;
+    a.part = (int64_t *)p;
+    p += b_part;
+    a.status = (int32_t *)p;
+    HIPCHK(hipMemsetAsync(a.status, 0, 16, s));
+    HIPCHK(launch_axt_plan(a, s));
+    HIPCHK(hipMemcpyAsync(&ws.h[0], a.pboff + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&ws.h[1], a.status, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    a.V = ws.h[0];
+    if ((int32_t)ws.h[1] & kAxtBadWindow)
+        return gac_fail(GAC_E_ARG, "gac_axt: a piece's blocks lie outside its chain (or its chain "
+                                   "index is out of range)");
+    return GAC_OK;
+}
+
+// the status word after a step, on the host
+static int axt_status(AxtWs &ws, const AxtArgs &a, hipStream_t s, int32_t *st) {
+    HIPCHK(hipMemcpyAsync(&ws.h[1], a.status, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    *st = (int32_t)ws.h[1];
+    return GAC_OK;
+}
+
+static int axt_bad_gap() {
+    return gac_fail(GAC_E_ARG, "gac_axt: a piece holds a negative or double-sided gap "
+                               "(cut chains with gac_axt_split)");
+}
+
+// measure into device arrays; extra: bytes the caller wants after acc in a2
+static int axt_measure_dev(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_window *h_pieces,
+                           const gac_window *d_pieces, int64_t n, int32_t *d_score,
+                           int64_t *d_match, int64_t *d_ali, int64_t *d_sym, bool own_out,
+                           hipStream_t s) {
+    AxtArgs a;
+    int rc = axt_plan(c, cs, ws, h_pieces, d_pieces, n, s, a);
+    if (rc != GAC_OK) return rc;
+    const size_t b_acc = up16((size_t)n * 32);
+    HIPCHK(arena_need(ws.a2, b_acc + (own_out ? 4 * up16((size_t)n * 8) : 0), s));
+    a.acc = (unsigned long long *)ws.a2.p;
+    if (own_out) {  // the host entry point's results, behind acc
+        char *p = ws.a2.p + b_acc;
+        d_score = (int32_t *)p;
+        d_match = (int64_t *)(p + up16((size_t)n * 8));
+        d_ali = (int64_t *)(p + 2 * up16((size_t)n * 8));
+        d_sym = (int64_t *)(p + 3 * up16((size_t)n * 8));
+    }
+    a.score = d_score;
+    a.match = d_match;
+    a.ali = d_ali;
+    a.sym = d_sym;
+    HIPCHK(hipMemsetAsync(a.acc, 0, (size_t)n * 32, s));
+    HIPCHK(launch_axt_stat(a, s));
+    int32_t st = 0;
+    rc = axt_status(ws, a, s, &st);
+    if (rc != GAC_OK) return rc;
+    if (st & kAxtBadGap) return axt_bad_gap();
+    return GAC_OK;
+}
+
+// render into device text; the pieces' rows are checked against out_bytes
+// before anything is written.  Returns with the render kernels enqueued.
+static int axt_render_dev(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_window *h_pieces,
+                          const gac_window *d_pieces, int64_t n, const int64_t *h_offsets,
+                          const int64_t *d_offsets, char *d_out, int64_t out_bytes, hipStream_t s) {
+    if (out_bytes < 0) return gac_fail(GAC_E_ARG, "gac_axt_render: negative out_bytes");
+    AxtArgs a;
+    int rc = axt_plan(c, cs, ws, h_pieces, d_pieces, n, s, a);
+    if (rc != GAC_OK) return rc;
+    const size_t b_S = up16((size_t)(a.V + 1) * 8), b_part = up16((size_t)(a.V / 2048 + 2) * 8);
+    const size_t b_off = up16((size_t)n * 8);
+    HIPCHK(arena_need(ws.a2, b_S + b_part + 2 * b_off, s));
+    char *p = ws.a2.p;
+    a.S = (int64_t *)p;
+    p += b_S;
+    a.part = (int64_t *)p;
+    p += b_part;
+    a.off = (int64_t *)p;
+    p += b_off;
+    if (h_offsets) {
+        HIPCHK(hipMemcpyAsync(p, h_offsets, (size_t)n * 8, hipMemcpyHostToDevice, s));
+        a.offsets = (const int64_t *)p;
+    } else {
+        a.offsets = d_offsets;
+    }
+    a.out = d_out;
+    a.out_bytes = out_bytes;
+    HIPCHK(launch_axt_place(a, s));
+    int32_t st = 0;
+    rc = axt_status(ws, a, s, &st);
+    if (rc != GAC_OK) return rc;
+    if (st & kAxtBadGap) return axt_bad_gap();
+    if (st & kAxtBadOut)
+        return gac_fail(GAC_E_ARG, "gac_axt_render: a piece's rows do not fit out_bytes (%lld)",
+                        (long long)out_bytes);
+    if (n && !d_out) return gac_fail(GAC_E_ARG, "NULL buffer");
+    HIPCHK(launch_axt_render(a, s));
+    return GAC_OK;
+}
+
+#define AXT_ENTRY(c, cs)                                                                   \
+    gac_clear_error();                                                                     \
+    if (!(c)) return gac_fail(GAC_E_ARG, "NULL context");                                  \
+    if (!(cs) || (cs)->ctx != (c)) return gac_fail(GAC_E_ARG, "NULL or orphaned chainset"); \
+    CTX_LOCK(c);                                                                           \
+    HIPCHK(hipSetDevice((c)->device));                                                     \
+    if (!(c)->axt) (c)->axt = new AxtWs()
+
+extern "C" int gac_axt_measure_device(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
+                                      int64_t n, int32_t *d_score, int64_t *d_match,
+                                      int64_t *d_ali, int64_t *d_sym, void *stream) {
+    AXT_ENTRY(c, cs);
+    if (n == 0) return GAC_OK;
+    if (n > 0 && (!d_pieces || !d_score || !d_match || !d_ali || !d_sym))
+        return gac_fail(GAC_E_ARG, "NULL buffer");
+    return axt_measure_dev(c, cs, *c->axt, nullptr, d_pieces, n, d_score, d_match, d_ali, d_sym,
+                           false, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int gac_axt_measure(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
+                               int64_t n, int32_t *score, int64_t *match, int64_t *ali,
+                               int64_t *sym) {
+    AXT_ENTRY(c, cs);
+    if (n == 0) return GAC_OK;
+    if (n > 0 && (!pieces || !score || !match || !ali || !sym))
+        return gac_fail(GAC_E_ARG, "NULL buffer");
+    hipStream_t s = c->stream;
+    int rc = axt_measure_dev(c, cs, *c->axt, pieces, nullptr, n, nullptr, nullptr, nullptr, nullptr,
+                             true, s);
+    if (rc != GAC_OK) return rc;
+    const char *p = c->axt->a2.p + up16((size_t)n * 32);
+    const size_t b = up16((size_t)n * 8);
+    HIPCHK(hipMemcpyAsync(score, p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(match, p + b, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ali, p + 2 * b, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sym, p + 3 * b, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return GAC_OK;
+}
+
+extern "C" int gac_axt_render_device(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
+                                     int64_t n, const int64_t *d_offsets, char *d_out,
+                                     int64_t out_bytes, void *stream) {
+    AXT_ENTRY(c, cs);
+    if (n == 0) return GAC_OK;
+    if (n > 0 && !d_pieces) return gac_fail(GAC_E_ARG, "NULL buffer");
+    return axt_render_dev(c, cs, *c->axt, nullptr, d_pieces, n, nullptr, d_offsets, d_out, out_bytes,
+                          stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int gac_axt_render(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
+                              int64_t n, const int64_t *offsets, char *out, int64_t out_bytes) {
+    AXT_ENTRY(c, cs);
+    if (n == 0) return GAC_OK;
+    if (n > 0 && (!pieces || !out)) return gac_fail(GAC_E_ARG, "NULL buffer");
+    if (out_bytes < 0) return gac_fail(GAC_E_ARG, "gac_axt_render: negative out_bytes");
+    hipStream_t s = c->stream;
+    AxtWs &ws = *c->axt;
+    // the caller's buffer goes to the device and comes back, so that the
+    // bytes between the pieces' rows stay what they were
+    HIPCHK(arena_need(ws.text, (size_t)out_bytes + 16, s));
+    HIPCHK(hipMemcpyAsync(ws.text.p, out, (size_t)out_bytes, hipMemcpyHostToDevice, s));
+    int rc = axt_render_dev(c, cs, ws, pieces, nullptr, n, offsets, nullptr, ws.text.p, out_bytes, s);
+    if (rc != GAC_OK) {
+        hipStreamSynchronize(s);
+        return rc;
+    }
+    HIPCHK(hipMemcpyAsync(out, ws.text.p, (size_t)out_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return GAC_OK;
+}
+
+// A render in flight (chainToAxt's batches): its own stream, workspace,
+// device text and pinned host text, so that two jobs alternate -- the host
+// formats one batch while the next is rendered and copied.
+struct gac_axt_job {
+    gac_ctx *ctx = nullptr;
+    hipStream_t st = nullptr;
+    AxtWs ws;
+    char *h_text = nullptr;  // pinned
+    int64_t cap = 0, bytes = 0;
+};
+
+static void job_release(gac_axt_job *j) {
+    if (j->st) {
+        hipStreamSynchronize(j->st);
+        hipStreamDestroy(j->st);
+    }
+    j->st = nullptr;
+    ws_free(j->ws);
+    if (j->h_text) hipHostFree(j->h_text);
+    j->h_text = nullptr;
+    j->cap = 0;
+}
+
+static void axt_release(gac_ctx *c) {
+    for (gac_axt_job *j : c->axt_jobs) {
+        job_release(j);
+        j->ctx = nullptr;
+    }
+    c->axt_jobs.clear();
+    if (c->axt) {
+        ws_free(*c->axt);
+        delete c->axt;
+        c->axt = nullptr;
+    }
+}
+
+static int job_text(gac_axt_job *j, int64_t bytes) {
+    if (bytes <= j->cap) return GAC_OK;
+    HIPCHK(hipStreamSynchronize(j->st));
+    if (j->h_text) hipHostFree(j->h_text);
+    j->h_text = nullptr;
+    j->cap = 0;
+    HIPCHK(hipHostMalloc((void **)&j->h_text, (size_t)bytes, hipHostMallocDefault));
+    j->cap = bytes;
+    return arena_need(j->ws.text, (size_t)bytes + 16, j->st) == hipSuccess
+               ? GAC_OK
+               : gac_fail(GAC_E_HIP, "gac_axt_job: no device memory for %lld text bytes",
+                          (long long)bytes);
+}
+
+extern "C" int gac_axt_job_open(gac_ctx *c, int64_t text_bytes, gac_axt_job **out) {
+    gac_clear_error();
+    if (!c || !out || text_bytes < 0) return gac_fail(GAC_E_ARG, "gac_axt_job_open: bad argument");
+    *out = nullptr;
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    gac_axt_job *j = new gac_axt_job();
+    j->ctx = c;
+    c->axt_jobs.push_back(j);
+    int rc = GAC_OK;
+    if (hipStreamCreateWithFlags(&j->st, hipStreamNonBlocking) != hipSuccess)
+        rc = gac_fail(GAC_E_HIP, "gac_axt_job_open: no stream");
+    if (rc == GAC_OK) rc = job_text(j, text_bytes > 0 ? text_bytes : 1);
+    if (rc != GAC_OK) {
+        gac_axt_job_close(j);
+        return rc;
+    }
+    *out = j;
+    return GAC_OK;
+}
+
+extern "C" int gac_axt_job_submit(gac_axt_job *j, const gac_chainset *cs, const gac_window *pieces,
+                                  int64_t n, const int64_t *offsets, int64_t bytes) {
+    gac_clear_error();
+    if (!j || !j->ctx) return gac_fail(GAC_E_ARG, "NULL or orphaned job");
+    gac_ctx *c = j->ctx;
+    if (!cs || cs->ctx != c) return gac_fail(GAC_E_ARG, "NULL or orphaned chainset");
+    if (bytes < 0 || n < 0 || (n > 0 && (!pieces || !offsets)))
+        return gac_fail(GAC_E_ARG, "gac_axt_job_submit: bad argument");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    j->bytes = 0;
+    if (n == 0 || bytes == 0) return GAC_OK;
+    int rc = job_text(j, bytes);
+    if (rc != GAC_OK) return rc;
+    rc = axt_render_dev(c, cs, j->ws, pieces, nullptr, n, offsets, nullptr, j->ws.text.p, bytes, j->st);
+    if (rc != GAC_OK) return rc;
+    HIPCHK(hipMemcpyAsync(j->h_text, j->ws.text.p, (size_t)bytes, hipMemcpyDeviceToHost, j->st));
+    j->bytes = bytes;
+    return GAC_OK;
+}
+
+extern "C" int gac_axt_job_wait(gac_axt_job *j, const char **text, int64_t *bytes) {
+    gac_clear_error();
+    if (!j || !j->ctx || !text) return gac_fail(GAC_E_ARG, "NULL or orphaned job");
+    HIPCHK(hipSetDevice(j->ctx->device));
+    HIPCHK(hipStreamSynchronize(j->st));  // (no context lock: the other job may be submitting)
+    *text = j->h_text;
+    if (bytes) *bytes = j->bytes;
+    return GAC_OK;
+}
+
+extern "C" void gac_axt_job_close(gac_axt_job *j) {
+    if (!j) return;
+    if (gac_ctx *c = j->ctx) {
+        CTX_LOCK(c);
+        hipSetDevice(c->device);
+        job_release(j);
+        c->axt_jobs.erase(std::remove(c->axt_jobs.begin(), c->axt_jobs.end(), j), c->axt_jobs.end());
+    }
+    delete j;
 }
 
 extern "C" int gac_score_ranges_device(gac_ctx *c, const gac_chainset *cs, const gac_range *d_ranges,

@@ -266,4 +266,34 @@ struct ComposeArgs {
     unsigned long long *total;  // [n_chains]
 };
 
+// k_axt_stat / k_axt_render (gac_axtout.hip): pieces (block windows of chains,
+// gac_window; t_start / t_end are not read) measured and written out as
+// alignment rows.  The pieces' blocks laid end to end are the call's virtual
+// blocks: pboff[p] = first virtual block of piece p, V = pboff[n].
+constexpr int kAxtBadWindow = 1;  // status[0] bits: a window outside its chain
+constexpr int kAxtBadGap = 2;     // a negative or double-sided gap inside a piece
+constexpr int kAxtBadOut = 4;     // a piece's rows outside the text buffer
+struct AxtArgs {
+    const uint2 *t_planes, *q_planes;
+    const uint32_t *t_nmask, *q_nmask, *t_lmask, *q_lmask;
+    const DChain *chains;
+    const int4 *blk;
+    int64_t n_chains;
+    const Window *pieces;  // [n]
+    int64_t n, V;
+    int64_t *pboff;        // [n + 1]
+    int64_t *part;         // [max(n, V) / 2048 + 2] the scans' workgroup totals
+    int32_t *status;       // [1] kAxtBad* bits (zeroed by the caller)
+    // measure
+    unsigned long long *acc;  // [n][4] score, match, ali, sym (zeroed by the caller)
+    int32_t *score;           // [n]
+    int64_t *match, *ali, *sym;
+    // render
+    int64_t *S;              // [V + 1] exclusive scan of the virtual blocks' columns
+    const int64_t *offsets;  // [n] byte offset of each piece's rows (null: packed in order)
+    int64_t *off;            // [n] the offsets used
+    char *out;
+    int64_t out_bytes;
+};
+
 }  // namespace gac

@@ -46,6 +46,7 @@ void gac_clear_error(void) { g_err[0] = 0; }
 const char *gac_last_error(void) { return g_err; }
 
 int gac_abi_version(void) { return GAC_ABI_VERSION; }
+int gac_abi_minor(void) { return GAC_ABI_MINOR; }
 
 /* ------------------------------------------------------------- file mapping */
 static int map_file(const char *path, gac_map *m, int populate);

@@ -185,6 +185,63 @@ class Engine:
             self.h, cs.handle, C.c_void_p(d_match), C.c_void_p(d_rep), C.c_void_p(d_total),
             C.c_void_p(stream) if stream else None))
 
+    # ---- alignment text (chainToAxt)
+    @staticmethod
+    def axt_split(t_seq, q_seq, q_strand, blk_off, blk_t, blk_q, blk_size,
+                  max_gap: int = 100) -> np.ndarray:
+        """chainToAxt's pieces of parsed chains (gac_axt_split; host only, no
+        device: callable on the class): int32 [n, 5] gac_window rows (chain,
+        tStart, tEnd, first block, blocks)."""
+        d, _arrs = Engine._desc(t_seq, q_seq, q_strand, blk_off, blk_t, blk_q, blk_size)
+        p = C.c_void_p()
+        n = C.c_int64()
+        check(lib().gac_axt_split(C.byref(d), int(max_gap), C.byref(p), C.byref(n)))
+        try:
+            out = np.zeros((n.value, 5), np.int32)
+            if n.value:
+                C.memmove(_p(out), p, n.value * 20)
+        finally:
+            lib().gac_axt_free(p)
+        return out
+
+    def axt_measure(self, cs: "ChainSet", pieces: np.ndarray):
+        """(score int32, match, ali, sym int64) of every piece (gac_axt_measure)."""
+        w = np.ascontiguousarray(np.asarray(pieces, dtype=np.int32).reshape(-1, 5))
+        n = w.shape[0]
+        score = np.zeros(n, np.int32)
+        match, ali, sym = (np.zeros(n, np.int64) for _ in range(3))
+        check(lib().gac_axt_measure(self.h, cs.handle, _p(w), n, _p(score), _p(match), _p(ali),
+                                    _p(sym)))
+        return score, match, ali, sym
+
+    def axt_measure_device(self, cs: "ChainSet", d_pieces: int, n: int, d_score: int, d_match: int,
+                           d_ali: int, d_sym: int, stream: int = 0) -> None:
+        check(lib().gac_axt_measure_device(
+            self.h, cs.handle, C.c_void_p(d_pieces), n, C.c_void_p(d_score), C.c_void_p(d_match),
+            C.c_void_p(d_ali), C.c_void_p(d_sym), C.c_void_p(stream) if stream else None))
+
+    def axt_render(self, cs: "ChainSet", pieces: np.ndarray, offsets=None, out=None,
+                   sym=None) -> np.ndarray:
+        """The pieces' rows, tSym '\\n' qSym '\\n' '\\n' each (gac_axt_render), into
+        the uint8 array `out` at byte `offsets` [n]; both None: packed in order
+        into a new array (sym: the pieces' column counts, measured if None)."""
+        w = np.ascontiguousarray(np.asarray(pieces, dtype=np.int32).reshape(-1, 5))
+        n = w.shape[0]
+        if out is None:
+            if sym is None:
+                sym = self.axt_measure(cs, w)[3]
+            out = np.zeros(int((2 * np.asarray(sym, np.int64) + 3).sum()), np.uint8)
+        off = None if offsets is None else np.ascontiguousarray(offsets, np.int64)
+        check(lib().gac_axt_render(self.h, cs.handle, _p(w), n, _p(off) if off is not None else None,
+                                   _p(out), out.size))
+        return out
+
+    def axt_render_device(self, cs: "ChainSet", d_pieces: int, n: int, d_offsets: int, d_out: int,
+                          out_bytes: int, stream: int = 0) -> None:
+        check(lib().gac_axt_render_device(
+            self.h, cs.handle, C.c_void_p(d_pieces), n, C.c_void_p(d_offsets) if d_offsets else None,
+            C.c_void_p(d_out), out_bytes, C.c_void_p(stream) if stream else None))
+
     def seq_index(self, side: int, name: str) -> int:
         return lib().gac_genome_seq_index(self.h, side, name.encode())
 

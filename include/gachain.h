@@ -31,6 +31,11 @@
  *                           index arithmetic, not a reverse-complemented copy)
  *   gac_chains_upload     <- chainRead            kent/src/lib/chain.c:256-346
  *                          (the caller hands over parsed chains as SoA arrays)
+ *   gac_axt_split         <- chainToAxt           kent/src/lib/chainToAxt.c:93-124
+ *   gac_axt_measure       <- axtScoreSym          kent/src/lib/axt.c:196-229
+ *                          + axtIdRatio           kent/src/hg/mouseStuff/chainToAxt/chainToAxt.c:69-89
+ *   gac_axt_render        <- loadSeqStrand        kent/src/hg/mouseStuff/chainToAxt/chainToAxt.c:48-67
+ *                          + axtFromBlocks        kent/src/lib/chainToAxt.c:14-91
  */
 #ifndef GACHAIN_H
 #define GACHAIN_H
@@ -44,6 +49,10 @@ extern "C" {
 #endif
 
 #define GAC_ABI_VERSION 1
+/* Bumped when entry points are added and nothing existing changes (a caller
+ * built against minor m runs with any library of minor >= m):
+ * 1 = the alignment text entry points (gac_axt_*). */
+#define GAC_ABI_MINOR 1
 
 /* return codes */
 #define GAC_OK 0
@@ -119,6 +128,7 @@ typedef struct gac_chainset_desc {
 
 /* ---- library / context ------------------------------------------------ */
 int gac_abi_version(void);
+int gac_abi_minor(void);
 /* Human-readable message of the last error on this thread. */
 const char *gac_last_error(void);
 /* Open a context on HIP device `device`.  Fails (GAC_E_HIP) if there is no
@@ -296,6 +306,76 @@ int gac_chain_composition_device(gac_ctx *ctx, const gac_chainset *cs, int64_t *
  * (0/0 = NaN) is dropped as there.  1 = keep, 0 = drop.  Host only. */
 int gac_antirepeat_pass(double score, const int64_t match[4], int64_t rep, int64_t total,
                         int min_score);
+
+/* ---- alignment text (chainToAxt) ------------------------------------------
+ * A piece is a window of consecutive blocks of one chain (gac_window: chain,
+ * first_block, n_blocks; t_start / t_end are informative and not read) that
+ * becomes one axt record.  The entry points take any block windows, so
+ * sub-chains of net fills can be fed later; a window holding a negative or
+ * double-sided gap is GAC_E_ARG.
+ *
+ * gac_axt_split cuts every chain of a parsed set where chainToAxt() does
+ * (kent/src/lib/chainToAxt.c:105-121, called with maxChain = BIGNUM as
+ * kent/src/hg/mouseStuff/chainToAxt/chainToAxt.c:108 does): before block b
+ * with previous block a, dq = b.qStart - a.qEnd, dt = b.tStart - a.tEnd, when
+ * (dq > 0 && dt > 0) || dt > max_gap || dq > max_gap.  Pieces come in file
+ * order; t_start / t_end are the piece's target span.  A negative dq or dt
+ * (undefined in the reference) is GAC_E_FORMAT and gac_last_error names the
+ * chain.  Host only; release *pieces with gac_axt_free. */
+int gac_axt_split(const gac_chainset_desc *d, int32_t max_gap, gac_window **pieces, int64_t *n);
+void gac_axt_free(gac_window *pieces);
+/* Per piece, what axtFromBlocks + axtScoreDnaDefault and axtIdRatio compute
+ * from the rendered rows (chainToAxt.c:28-40,89; kent/src/lib/axt.c:196-229,
+ * 423-458; chainToAxt/chainToAxt.c:69-89), without rendering them:
+ *   sym[p]   = columns: block sizes + inner gap lengths (symCount)
+ *   score[p] = sum over blocks of the blastz default matrix on the letters
+ *              (case-blind, a column with an N scores 0) - sum over inner
+ *              gaps of length L > 0 of (400 + 30 L); summed in int64 and
+ *              narrowed to int32 as the reference's int wraps.  The default
+ *              matrix always: gac_set_scoring is neither needed nor read.
+ *   ali[p]   = columns without a dash = sum of the block sizes
+ *   match[p] = of those, letters equal case-blind, N against N included
+ * (idRatio = match ? (double)match / ali : 0.0).  Both sides need the
+ * soft-mask plane (GAC_E_STATE); a NULL or orphaned set, or a window outside
+ * its chain, is GAC_E_ARG; n == 0 writes nothing.  Host buffers, synchronous. */
+int gac_axt_measure(gac_ctx *ctx, const gac_chainset *cs, const gac_window *pieces, int64_t n,
+                    int32_t *score, int64_t *match, int64_t *ali, int64_t *sym);
+/* The same with pieces and results in device memory, on `stream` (NULL: the
+ * context's).  The call waits on the stream for its checks; the results stay
+ * on the device. */
+int gac_axt_measure_device(gac_ctx *ctx, const gac_chainset *cs, const gac_window *d_pieces,
+                           int64_t n, int32_t *d_score, int64_t *d_match, int64_t *d_ali,
+                           int64_t *d_sym, void *stream);
+/* The rows of every piece as axtFromBlocks fills them (chainToAxt.c:58-86)
+ * from twoBitReadSeqFragExt(doMask=TRUE) text (chainToAxt/chainToAxt.c:48-67:
+ * 'ACGTN', lower case in mask runs, '-' chains reverse-complemented with case
+ * and N travelling with the base), laid out for axtWrite (axt.c:110-114):
+ *   out[offsets[p] ..] = tSym '\n' qSym '\n' '\n'     (2 * sym[p] + 3 bytes)
+ * offsets NULL: the pieces packed in order from byte 0.  No other byte of out
+ * is changed.  A piece whose rows would pass out_bytes is GAC_E_ARG and
+ * nothing is written.  Host buffers, synchronous (the buffer travels to the
+ * device and back: batches go through gac_axt_job). */
+int gac_axt_render(gac_ctx *ctx, const gac_chainset *cs, const gac_window *pieces, int64_t n,
+                   const int64_t *offsets, char *out, int64_t out_bytes);
+/* The same with pieces, offsets and text in device memory, on `stream`; waits
+ * on the stream for its checks and returns with the rendering enqueued. */
+int gac_axt_render_device(gac_ctx *ctx, const gac_chainset *cs, const gac_window *d_pieces,
+                          int64_t n, const int64_t *d_offsets, char *d_out, int64_t out_bytes,
+                          void *stream);
+/* One render in flight: a stream, device text and pinned host text of its
+ * own.  submit checks the pieces, then enqueues gac_axt_render of `bytes` of
+ * text and its copy to the job's pinned buffer and returns; wait gives the
+ * text once it has arrived (valid until the job's next submit; bytes of it
+ * that no piece's rows cover are unspecified).  Two jobs
+ * used in turn overlap the host's work on one batch with the next batch's
+ * rendering and copy.  text_bytes: initial capacity (grown by a larger
+ * submit).  Close jobs before gac_close. */
+typedef struct gac_axt_job gac_axt_job;
+int gac_axt_job_open(gac_ctx *ctx, int64_t text_bytes, gac_axt_job **out);
+int gac_axt_job_submit(gac_axt_job *job, const gac_chainset *cs, const gac_window *pieces,
+                       int64_t n, const int64_t *offsets, int64_t bytes);
+int gac_axt_job_wait(gac_axt_job *job, const char **text, int64_t *bytes);
+void gac_axt_job_close(gac_axt_job *job);
 
 /* ---- caller text (the kent in-process API's char* entry points) ---------
  * chainScoreBlock / axtScoreUngapped (kent/src/lib/chainConnect.c:14-22,
