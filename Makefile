@@ -33,7 +33,7 @@ EXECDIR  := $(PKG)/libexec
 # GB/s for the genome uploads on the box, profiles/r02f_*), and execs it --
 # before anything touches the GPU.  Either can be overridden from outside.
 # NetFilterNonNested.perl, chainSort and chainMergeSort are host-only: in bin/.
-GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt
+GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt netToAxt
 HOST_TOOLS := NetFilterNonNested.perl chainSort chainMergeSort
 TOOLS    := $(addprefix $(EXECDIR)/,$(GPU_TOOLS)) $(addprefix $(BINDIR)/,$(GPU_TOOLS)) \
             $(addprefix $(BINDIR)/,$(HOST_TOOLS))

@@ -175,6 +175,22 @@ _PROTOS = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "gac_axt_job_wait": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
     "gac_axt_job_close": (None, [C.c_void_p]),
+    "gac_axt_cut": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.POINTER(C.c_void_p),
+                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "gac_axt_measure_clip": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p]),
+    "gac_axt_measure_clip_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p]),
+    "gac_axt_render_clip": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
+    "gac_axt_render_clip_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
+                  C.c_void_p]),
+    "gac_axt_job_submit_clip": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "gac_chains_upload": (C.c_int, [C.c_void_p, C.POINTER(ChainsetDesc), C.POINTER(C.c_void_p)]),
     "gac_chains_reupload": (C.c_int, [C.c_void_p, C.POINTER(ChainsetDesc), C.c_void_p]),
     "gac_chains_free": (None, [C.c_void_p]),

@@ -26,6 +26,10 @@
 //                 bit reversal for '-') and stores them with one 16-byte
 //                 store; only a run's first and last window fall back to
 //                 4-byte and single-byte stores.
+//   k_cut_*       netToAxt's ranges (chain, tStart, tEnd) to clipped pieces
+//                 (gac_axt_cut): see the section near the end.  The kernels
+//                 above are templates on kClip, which makes a piece's first
+//                 and last block honour its t_start / t_end (gac_axt_*_clip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -132,7 +136,9 @@ __global__ void __launch_bounds__(256) k_axt_scan_apply(long long *arr, int64_t 
 
 // ------------------------------------------------------------------ plan
 // One lane per piece: its window checked against its chain; pboff[i] = its
-// blocks (0 for a bad one, so no later kernel touches it).
+// blocks (0 for a bad one, so no later kernel touches it).  kClip: t_start /
+// t_end must leave a base of the first and of the last block.
+template <bool kClip>
 __global__ void __launch_bounds__(256) k_axt_plan(AxtArgs a) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.n) return;
@@ -143,8 +149,19 @@ __global__ void __launch_bounds__(256) k_axt_plan(AxtArgs a) {
         const int32_t have = a.chains[w.chain].nblk;
         bad = (int64_t)w.first + w.nblk > have;
     }
-    if (bad) atomicOr(a.status, kAxtBadWindow);
-    else nb = w.nblk;
+    if (bad) {
+        atomicOr(a.status, kAxtBadWindow);
+    } else if (kClip && w.nblk > 0) {
+        const int4 *b = a.blk + a.chains[w.chain].blk_off + w.first;
+        const int4 f = b[0], l = b[w.nblk - 1];
+        const long long fe = (long long)f.x + (f.z & kSizeMask), le = (long long)l.x + (l.z & kSizeMask);
+        const long long s = w.t_start > f.x ? w.t_start : f.x;  // the first block's start
+        const long long e = w.t_end < le ? w.t_end : le;        // the last block's end
+        // (one block: both cuts are its own; more: the first keeps its end, the last its start)
+        bad = w.nblk == 1 ? s >= e : (s >= fe || e <= l.x);
+        if (bad) atomicOr(a.status, kAxtBadClip);
+    }
+    if (!bad) nb = w.nblk;
     a.pboff[i] = nb;
 }
 
@@ -158,6 +175,11 @@ struct AxtLoc {
     DChain ch;
 };
 
+// kClip: the piece's first block starts at max(tStart, t_start), its last ends
+// at min(tEnd, t_end), the query following (chainFastSubsetOnT, chain.c:513-522);
+// k_axt_plan has checked that both keep a base.  Inner gaps lie between
+// unclipped block ends.
+template <bool kClip>
 __device__ __forceinline__ AxtLoc axt_locate(const AxtArgs &a, int64_t v) {
     AxtLoc L;
     int64_t lo = 0, hi = a.n - 1;  // last p with pboff[p] <= v (empty pieces share an offset)
@@ -187,6 +209,16 @@ __device__ __forceinline__ AxtLoc axt_locate(const AxtArgs &a, int64_t v) {
             L.gap = (int)(dt + dq);
             L.tgap = dt > 0;
         }
+    }
+    if (kClip) {
+        const int end = L.bk.x + L.size;
+        if (v == L.v0 && w.t_start > L.bk.x) {
+            const int head = w.t_start - L.bk.x;
+            L.bk.x += head;
+            L.bk.y += head;
+            L.size -= head;
+        }
+        if (v - L.v0 == w.nblk - 1 && w.t_end < end) L.size -= end - w.t_end;
     }
     return L;
 }
@@ -229,6 +261,7 @@ __device__ __forceinline__ void stat_flush(unsigned long long (*acc)[4], int lan
     }
 }
 
+template <bool kClip>
 __global__ void __launch_bounds__(256) k_axt_stat(AxtArgs a) {
     __shared__ StatWave s_w[kWavesPerWG];
     __shared__ unsigned long long s_acc[kAxtSlots][4];  // score, match, ali, sym
@@ -246,7 +279,7 @@ __global__ void __launch_bounds__(256) k_axt_stat(AxtArgs a) {
         int len = 0, lenq = 0, slot = 0;
         long long tpos = 0, qpos = 0;
         if (v < a.V) {
-            const AxtLoc L = axt_locate(a, v);
+            const AxtLoc L = axt_locate<kClip>(a, v);
             if (L.bad) atomicOr(a.status, kAxtBadGap);
             len = L.size;
             const bool minus = L.ch.qbase < 0;
@@ -357,10 +390,11 @@ __global__ void __launch_bounds__(256) k_axt_fin(AxtArgs a) {
 
 // ---------------------------------------------------------------- columns
 // S[v] = columns of virtual block v (inner gap + size), scanned afterwards.
+template <bool kClip>
 __global__ void __launch_bounds__(256) k_axt_cols(AxtArgs a) {
     const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= a.V) return;
-    const AxtLoc L = axt_locate(a, v);
+    const AxtLoc L = axt_locate<kClip>(a, v);
     if (L.bad) atomicOr(a.status, kAxtBadGap);
     a.S[v] = (long long)L.size + L.gap;
 }
@@ -401,6 +435,7 @@ struct RenderWave {
 // 4 bits to the low bit of 4 bytes
 __device__ __forceinline__ uint32_t spread4(uint32_t x) { return (x * 0x00204081u) & 0x01010101u; }
 
+template <bool kClip>
 __global__ void __launch_bounds__(256) k_axt_render(AxtArgs a) {
     __shared__ RenderWave s_w[kWavesPerWG];
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
@@ -412,7 +447,7 @@ __global__ void __launch_bounds__(256) k_axt_render(AxtArgs a) {
     int nwt = 0, w = 0, dt = 0, dq = 0;
     long long at = 0, aq = 0, st = 0, sq = 0;
     if (v < a.V) {
-        const AxtLoc L = axt_locate(a, v);
+        const AxtLoc L = axt_locate<kClip>(a, v);
         const long long s0 = a.S[L.v0], sym = a.S[a.pboff[L.p + 1]] - s0;
         const long long col = a.S[v] - s0;
         w = L.size + L.gap;
@@ -537,6 +572,113 @@ __global__ void __launch_bounds__(256) k_axt_render(AxtArgs a) {
     }
 }
 
+// -------------------------------------------------------------------- cut
+// Ranges to clipped pieces (gac_axt_cut; netToAxt's chainSubsetOnT +
+// chainToAxt, kent/src/lib/chain.c:471-558, kent/src/lib/chainToAxt.c:93-124).
+// Only k_cut_find has a lane per range (two binary searches); the rest is cut
+// over the selected blocks, so a range costs what its blocks cost.
+
+// One lane per range: the blocks chainSubsetOnT selects -- from the first with
+// tEnd > t_start (chain.c:482-486) up to the first with tStart >= t_end (:510).
+__global__ void __launch_bounds__(256) k_cut_find(AxtCutArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n) return;
+    const Range r = a.ranges[i];
+    int first = 0;
+    long long cnt = 0;
+    if (r.chain < 0 || r.chain >= a.n_chains) {
+        atomicOr(a.status, kAxtBadWindow);
+    } else if (r.t_start < r.t_end) {
+        const DChain ch = a.chains[r.chain];
+        const int4 *b = a.blk + ch.blk_off;
+        int lo = 0, hi = ch.nblk;  // first block with tEnd > t_start
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const int4 k = b[mid];
+            if ((long long)k.x + (k.z & kSizeMask) > r.t_start) hi = mid;
+            else lo = mid + 1;
+        }
+        first = lo;
+        hi = ch.nblk;  // first block (from there on) with tStart >= t_end
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (b[mid].x >= r.t_end) hi = mid;
+            else lo = mid + 1;
+        }
+        cnt = lo - first;
+    }
+    a.rfirst[i] = first;
+    a.rboff[i] = cnt;
+}
+
+// virtual block v: its range and its index inside the range's window
+__device__ __forceinline__ int64_t cut_locate(const AxtCutArgs &a, int64_t v, int64_t &j) {
+    int64_t lo = 0, hi = a.n - 1;  // last r with rboff[r] <= v (empty ranges share an offset)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) >> 1;
+        if (a.rboff[mid] <= v) lo = mid;
+        else hi = mid - 1;
+    }
+    j = v - a.rboff[lo];
+    return lo;
+}
+
+// One lane per virtual block: 1 where a piece starts (chainToAxt.c:109-111 with
+// maxChain = BIGNUM; the reference compares ints).
+__global__ void __launch_bounds__(256) k_cut_flag(AxtCutArgs a) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= a.V) return;
+    int64_t j;
+    const int64_t r = cut_locate(a, v, j);
+    long long f = 1;
+    if (j > 0) {
+        const int4 *b = a.blk + a.chains[a.ranges[r].chain].blk_off + a.rfirst[r] + j;
+        const int4 k = b[0], pk = b[-1];
+        const int psz = pk.z & kSizeMask;
+        const int dt = k.x - (pk.x + psz), dq = k.y - (pk.y + psz);
+        if (dt < 0 || dq < 0) {
+            atomicOr(a.status, kAxtBadGap);
+            atomicMin(a.status + 1, (int)r);
+        }
+        f = (dq > 0 && dt > 0) || dt > a.max_gap || dq > a.max_gap;
+    }
+    a.pidx[v] = f;
+}
+
+// One lane per virtual block, after the scan of the flags (block v lies in
+// piece pidx[v + 1] - 1 and starts it when pidx[v + 1] > pidx[v]): a piece's
+// head writes chain, first block and the clipped start, its tail the clipped
+// end and its own chain-local index + 1 (k_cut_close turns that into a count).
+__global__ void __launch_bounds__(256) k_cut_emit(AxtCutArgs a) {
+    const int64_t v = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= a.V) return;
+    int64_t j;
+    const int64_t r = cut_locate(a, v, j);
+    const Range rg = a.ranges[r];
+    const int cb = a.rfirst[r] + (int)j;
+    const int4 k = a.blk[a.chains[rg.chain].blk_off + cb];
+    const int64_t here = a.pidx[v], next = a.pidx[v + 1];
+    Window *w = a.pieces + (next - 1);
+    if (next > here) {
+        w->chain = rg.chain;
+        w->first = cb;
+        w->t_start = k.x > rg.t_start ? k.x : rg.t_start;
+    }
+    // (pidx[V + 1] is never read: v + 1 == V is the last range's last block)
+    if (v + 1 == a.rboff[r + 1] || a.pidx[v + 2] > next) {
+        const int end = k.x + (k.z & kSizeMask);
+        w->t_end = end < rg.t_end ? end : rg.t_end;
+        w->nblk = cb + 1;
+    }
+}
+
+// lanes [0, P): the piece's block count; lanes [0, n]: first[r]
+__global__ void __launch_bounds__(256) k_cut_close(AxtCutArgs a) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < a.P) a.pieces[i].nblk -= a.pieces[i].first;
+    if (i <= a.n) a.first[i] = i < a.n ? a.pidx[a.rboff[i]] : a.P;
+}
+
 inline unsigned grid256(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
@@ -551,9 +693,32 @@ static hipError_t axt_scan(long long *arr, int64_t m, long long *part, hipStream
     return hipGetLastError();
 }
 
+// gac_axt_cut in three steps, the host reading one count between them:
+// the ranges' windows and rboff (rboff[n] = V) ...
+hipError_t launch_axt_cut_find(const AxtCutArgs &a, hipStream_t s) {
+    if (a.n > 0) hipLaunchKernelGGL(k_cut_find, dim3(grid256(a.n)), dim3(256), 0, s, a);
+    return axt_scan((long long *)a.rboff, a.n, (long long *)a.part, s);
+}
+
+// ... the break flags and their scan (pidx[V] = P, the pieces) ...
+hipError_t launch_axt_cut_flag(const AxtCutArgs &a, hipStream_t s) {
+    if (a.V > 0) hipLaunchKernelGGL(k_cut_flag, dim3(grid256(a.V)), dim3(256), 0, s, a);
+    return axt_scan((long long *)a.pidx, a.V, (long long *)a.part, s);
+}
+
+// ... and the pieces and first[0 .. n]
+hipError_t launch_axt_cut_emit(const AxtCutArgs &a, hipStream_t s) {
+    if (a.V > 0) hipLaunchKernelGGL(k_cut_emit, dim3(grid256(a.V)), dim3(256), 0, s, a);
+    const int64_t m = a.P > a.n + 1 ? a.P : a.n + 1;
+    hipLaunchKernelGGL(k_cut_close, dim3(grid256(m)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 // pieces checked, pboff scanned (pboff[n] = V, the virtual blocks)
 hipError_t launch_axt_plan(const AxtArgs &a, hipStream_t s) {
-    if (a.n > 0) hipLaunchKernelGGL(k_axt_plan, dim3(grid256(a.n)), dim3(256), 0, s, a);
+    if (a.n > 0)
+        hipLaunchKernelGGL(a.clip ? k_axt_plan<true> : k_axt_plan<false>, dim3(grid256(a.n)), dim3(256),
+                           0, s, a);
     return axt_scan((long long *)a.pboff, a.n, (long long *)a.part, s);
 }
 
@@ -561,8 +726,8 @@ hipError_t launch_axt_plan(const AxtArgs &a, hipStream_t s) {
 hipError_t launch_axt_stat(const AxtArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     if (a.V > 0)
-        hipLaunchKernelGGL(k_axt_stat, dim3((unsigned)((a.V + kAxtSlots - 1) / kAxtSlots)), dim3(256),
-                           0, s, a);
+        hipLaunchKernelGGL(a.clip ? k_axt_stat<true> : k_axt_stat<false>,
+                           dim3((unsigned)((a.V + kAxtSlots - 1) / kAxtSlots)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_axt_fin, dim3(grid256(a.n)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
@@ -570,7 +735,9 @@ hipError_t launch_axt_stat(const AxtArgs &a, hipStream_t s) {
 // S, the pieces' offsets and the buffer check (status)
 hipError_t launch_axt_place(const AxtArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
-    if (a.V > 0) hipLaunchKernelGGL(k_axt_cols, dim3(grid256(a.V)), dim3(256), 0, s, a);
+    if (a.V > 0)
+        hipLaunchKernelGGL(a.clip ? k_axt_cols<true> : k_axt_cols<false>, dim3(grid256(a.V)), dim3(256),
+                           0, s, a);
     const hipError_t e = axt_scan((long long *)a.S, a.V, (long long *)a.part, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_axt_place, dim3(grid256(a.n)), dim3(256), 0, s, a);
@@ -581,8 +748,8 @@ hipError_t launch_axt_render(const AxtArgs &a, hipStream_t s) {
     if (a.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_axt_seps, dim3(grid256(a.n)), dim3(256), 0, s, a);
     if (a.V > 0)
-        hipLaunchKernelGGL(k_axt_render, dim3((unsigned)((a.V + kAxtSlots - 1) / kAxtSlots)),
-                           dim3(256), 0, s, a);
+        hipLaunchKernelGGL(a.clip ? k_axt_render<true> : k_axt_render<false>,
+                           dim3((unsigned)((a.V + kAxtSlots - 1) / kAxtSlots)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -94,6 +94,9 @@ hipError_t launch_axt_plan(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_stat(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_place(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_render(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_cut_find(const AxtCutArgs &a, hipStream_t s);
+hipError_t launch_axt_cut_flag(const AxtCutArgs &a, hipStream_t s);
+hipError_t launch_axt_cut_emit(const AxtCutArgs &a, hipStream_t s);
 }  // namespace gac
 
 using namespace gac;
@@ -3268,7 +3271,7 @@ static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 // Step one.  pieces: in host memory (copied) or already on the device.  On
 // return a holds the genome, set and plan fields and a.V; status is zero.
 static int axt_plan(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_window *h_pieces,
-                    const gac_window *d_pieces, int64_t n, hipStream_t s, AxtArgs &a) {
+                    const gac_window *d_pieces, int64_t n, bool clip, hipStream_t s, AxtArgs &a) {
     if (!c->g[0].final || !c->g[1].final || !c->g[0].lmask || !c->g[1].lmask)
         return gac_fail(GAC_E_STATE, "gac_axt: both genome sides need the soft-mask plane "
                                      "(gac_genome_want_softmask before loading)");
@@ -3290,6 +3293,7 @@ static int axt_plan(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_win
     a.blk = cs->blk;
     a.n_chains = cs->n_chains;
     a.n = n;
+    a.clip = clip;
     if (h_pieces) {
         HIPCHK(hipMemcpyAsync(p, h_pieces, (size_t)n * sizeof(Window), hipMemcpyHostToDevice, s));
         a.pieces = (const Window *)p;
@@ -3311,6 +3315,9 @@ static int axt_plan(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_win
     if ((int32_t)ws.h[1] & kAxtBadWindow)
         return gac_fail(GAC_E_ARG, "gac_axt: a piece's blocks lie outside its chain (or its chain "
                                    "index is out of range)");
+    if ((int32_t)ws.h[1] & kAxtBadClip)
+        return gac_fail(GAC_E_ARG, "gac_axt: a piece's t_start / t_end leave its first or last "
+                                   "block empty");
     return GAC_OK;
 }
 
@@ -3331,9 +3338,9 @@ static int axt_bad_gap() {
 static int axt_measure_dev(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_window *h_pieces,
                            const gac_window *d_pieces, int64_t n, int32_t *d_score,
                            int64_t *d_match, int64_t *d_ali, int64_t *d_sym, bool own_out,
-                           hipStream_t s) {
+                           bool clip, hipStream_t s) {
     AxtArgs a;
-    int rc = axt_plan(c, cs, ws, h_pieces, d_pieces, n, s, a);
+    int rc = axt_plan(c, cs, ws, h_pieces, d_pieces, n, clip, s, a);
     if (rc != GAC_OK) return rc;
     const size_t b_acc = up16((size_t)n * 32);
     HIPCHK(arena_need(ws.a2, b_acc + (own_out ? 4 * up16((size_t)n * 8) : 0), s));
@@ -3362,10 +3369,11 @@ static int axt_measure_dev(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const 
 // before anything is written.  Returns with the render kernels enqueued.
 static int axt_render_dev(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_window *h_pieces,
                           const gac_window *d_pieces, int64_t n, const int64_t *h_offsets,
-                          const int64_t *d_offsets, char *d_out, int64_t out_bytes, hipStream_t s) {
+                          const int64_t *d_offsets, char *d_out, int64_t out_bytes, bool clip,
+                          hipStream_t s) {
     if (out_bytes < 0) return gac_fail(GAC_E_ARG, "gac_axt_render: negative out_bytes");
     AxtArgs a;
-    int rc = axt_plan(c, cs, ws, h_pieces, d_pieces, n, s, a);
+    int rc = axt_plan(c, cs, ws, h_pieces, d_pieces, n, clip, s, a);
     if (rc != GAC_OK) return rc;
     const size_t b_S = up16((size_t)(a.V + 1) * 8), b_part = up16((size_t)(a.V / 2048 + 2) * 8);
     const size_t b_off = up16((size_t)n * 8);
@@ -3406,27 +3414,27 @@ static int axt_render_dev(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const g
     HIPCHK(hipSetDevice((c)->device));                                                     \
     if (!(c)->axt) (c)->axt = new AxtWs()
 
-extern "C" int gac_axt_measure_device(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
-                                      int64_t n, int32_t *d_score, int64_t *d_match,
-                                      int64_t *d_ali, int64_t *d_sym, void *stream) {
+// The entry points; clip: the _clip forms, which read t_start / t_end.
+static int axt_measure_device_x(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
+                                int64_t n, int32_t *d_score, int64_t *d_match, int64_t *d_ali,
+                                int64_t *d_sym, void *stream, bool clip) {
     AXT_ENTRY(c, cs);
     if (n == 0) return GAC_OK;
     if (n > 0 && (!d_pieces || !d_score || !d_match || !d_ali || !d_sym))
         return gac_fail(GAC_E_ARG, "NULL buffer");
     return axt_measure_dev(c, cs, *c->axt, nullptr, d_pieces, n, d_score, d_match, d_ali, d_sym,
-                           false, stream ? (hipStream_t)stream : c->stream);
+                           false, clip, stream ? (hipStream_t)stream : c->stream);
 }
 
-extern "C" int gac_axt_measure(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
-                               int64_t n, int32_t *score, int64_t *match, int64_t *ali,
-                               int64_t *sym) {
+static int axt_measure_x(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces, int64_t n,
+                         int32_t *score, int64_t *match, int64_t *ali, int64_t *sym, bool clip) {
     AXT_ENTRY(c, cs);
     if (n == 0) return GAC_OK;
     if (n > 0 && (!pieces || !score || !match || !ali || !sym))
         return gac_fail(GAC_E_ARG, "NULL buffer");
     hipStream_t s = c->stream;
     int rc = axt_measure_dev(c, cs, *c->axt, pieces, nullptr, n, nullptr, nullptr, nullptr, nullptr,
-                             true, s);
+                             true, clip, s);
     if (rc != GAC_OK) return rc;
     const char *p = c->axt->a2.p + up16((size_t)n * 32);
     const size_t b = up16((size_t)n * 8);
@@ -3438,18 +3446,18 @@ extern "C" int gac_axt_measure(gac_ctx *c, const gac_chainset *cs, const gac_win
     return GAC_OK;
 }
 
-extern "C" int gac_axt_render_device(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
-                                     int64_t n, const int64_t *d_offsets, char *d_out,
-                                     int64_t out_bytes, void *stream) {
+static int axt_render_device_x(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
+                               int64_t n, const int64_t *d_offsets, char *d_out, int64_t out_bytes,
+                               void *stream, bool clip) {
     AXT_ENTRY(c, cs);
     if (n == 0) return GAC_OK;
     if (n > 0 && !d_pieces) return gac_fail(GAC_E_ARG, "NULL buffer");
     return axt_render_dev(c, cs, *c->axt, nullptr, d_pieces, n, nullptr, d_offsets, d_out, out_bytes,
-                          stream ? (hipStream_t)stream : c->stream);
+                          clip, stream ? (hipStream_t)stream : c->stream);
 }
 
-extern "C" int gac_axt_render(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
-                              int64_t n, const int64_t *offsets, char *out, int64_t out_bytes) {
+static int axt_render_x(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces, int64_t n,
+                        const int64_t *offsets, char *out, int64_t out_bytes, bool clip) {
     AXT_ENTRY(c, cs);
     if (n == 0) return GAC_OK;
     if (n > 0 && (!pieces || !out)) return gac_fail(GAC_E_ARG, "NULL buffer");
@@ -3460,13 +3468,149 @@ extern "C" int gac_axt_render(gac_ctx *c, const gac_chainset *cs, const gac_wind
     // bytes between the pieces' rows stay what they were
     HIPCHK(arena_need(ws.text, (size_t)out_bytes + 16, s));
     HIPCHK(hipMemcpyAsync(ws.text.p, out, (size_t)out_bytes, hipMemcpyHostToDevice, s));
-    int rc = axt_render_dev(c, cs, ws, pieces, nullptr, n, offsets, nullptr, ws.text.p, out_bytes, s);
+    int rc = axt_render_dev(c, cs, ws, pieces, nullptr, n, offsets, nullptr, ws.text.p, out_bytes,
+                            clip, s);
     if (rc != GAC_OK) {
         hipStreamSynchronize(s);
         return rc;
     }
     HIPCHK(hipMemcpyAsync(out, ws.text.p, (size_t)out_bytes, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    return GAC_OK;
+}
+
+extern "C" int gac_axt_measure_device(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
+                                      int64_t n, int32_t *d_score, int64_t *d_match,
+                                      int64_t *d_ali, int64_t *d_sym, void *stream) {
+    return axt_measure_device_x(c, cs, d_pieces, n, d_score, d_match, d_ali, d_sym, stream, false);
+}
+
+extern "C" int gac_axt_measure_clip_device(gac_ctx *c, const gac_chainset *cs,
+                                           const gac_window *d_pieces, int64_t n, int32_t *d_score,
+                                           int64_t *d_match, int64_t *d_ali, int64_t *d_sym,
+                                           void *stream) {
+    return axt_measure_device_x(c, cs, d_pieces, n, d_score, d_match, d_ali, d_sym, stream, true);
+}
+
+extern "C" int gac_axt_measure(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
+                               int64_t n, int32_t *score, int64_t *match, int64_t *ali,
+                               int64_t *sym) {
+    return axt_measure_x(c, cs, pieces, n, score, match, ali, sym, false);
+}
+
+extern "C" int gac_axt_measure_clip(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
+                                    int64_t n, int32_t *score, int64_t *match, int64_t *ali,
+                                    int64_t *sym) {
+    return axt_measure_x(c, cs, pieces, n, score, match, ali, sym, true);
+}
+
+extern "C" int gac_axt_render_device(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
+                                     int64_t n, const int64_t *d_offsets, char *d_out,
+                                     int64_t out_bytes, void *stream) {
+    return axt_render_device_x(c, cs, d_pieces, n, d_offsets, d_out, out_bytes, stream, false);
+}
+
+extern "C" int gac_axt_render_clip_device(gac_ctx *c, const gac_chainset *cs,
+                                          const gac_window *d_pieces, int64_t n,
+                                          const int64_t *d_offsets, char *d_out, int64_t out_bytes,
+                                          void *stream) {
+    return axt_render_device_x(c, cs, d_pieces, n, d_offsets, d_out, out_bytes, stream, true);
+}
+
+extern "C" int gac_axt_render(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
+                              int64_t n, const int64_t *offsets, char *out, int64_t out_bytes) {
+    return axt_render_x(c, cs, pieces, n, offsets, out, out_bytes, false);
+}
+
+extern "C" int gac_axt_render_clip(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
+                                   int64_t n, const int64_t *offsets, char *out, int64_t out_bytes) {
+    return axt_render_x(c, cs, pieces, n, offsets, out, out_bytes, true);
+}
+
+// Ranges to clipped pieces.  Two host waits: for V (the selected blocks, which
+// size the flag array and its kernels) and for P (which sizes the result).
+extern "C" int gac_axt_cut(gac_ctx *c, const gac_chainset *cs, const gac_range *ranges, int64_t n,
+                           int32_t max_gap, gac_window **pieces, int64_t **first,
+                           int64_t *n_pieces) {
+    if (pieces) *pieces = nullptr;
+    if (first) *first = nullptr;
+    if (n_pieces) *n_pieces = 0;
+    AXT_ENTRY(c, cs);
+    if (!pieces || !first || !n_pieces || n < 0 || n >= INT32_MAX || (n > 0 && !ranges))
+        return gac_fail(GAC_E_ARG, "gac_axt_cut: bad argument");
+    AxtWs &ws = *c->axt;
+    hipStream_t s = c->stream;
+    if (!ws.h) HIPCHK(hipHostMalloc((void **)&ws.h, 64, hipHostMallocDefault));
+    const size_t b_rg = up16((size_t)n * sizeof(Range)), b_rf = up16((size_t)n * 4);
+    const size_t b_rboff = up16((size_t)(n + 1) * 8), b_first = b_rboff;
+    HIPCHK(arena_need(ws.a1, b_rg + b_rf + b_rboff + b_first + 16, s));
+    AxtCutArgs a;
+    memset(&a, 0, sizeof(a));
+    a.chains = cs->chains;
+    a.blk = cs->blk;
+    a.n_chains = cs->n_chains;
+    a.n = n;
+    a.max_gap = max_gap;
+    char *p = ws.a1.p;
+    a.ranges = (const Range *)p;
+    p += b_rg;
+    a.rfirst = (int32_t *)p;
+    p += b_rf;
+    a.rboff = (int64_t *)p;
+    p += b_rboff;
+    a.first = (int64_t *)p;
+    p += b_first;
+    a.status = (int32_t *)p;
+    // the scans' workgroup totals, first for n and then for V elements, lie in a2
+    HIPCHK(arena_need(ws.a2, up16((size_t)(n / 2048 + 2) * 8), s));
+    a.part = (int64_t *)ws.a2.p;
+    if (n)
+        HIPCHK(hipMemcpyAsync((void *)a.ranges, ranges, (size_t)n * sizeof(Range),
+                              hipMemcpyHostToDevice, s));
+    ws.h[2] = INT32_MAX;
+    ws.h[2] <<= 32;  // status[0] = 0, status[1] = INT32_MAX
+    HIPCHK(hipMemcpyAsync(a.status, &ws.h[2], 8, hipMemcpyHostToDevice, s));
+    HIPCHK(launch_axt_cut_find(a, s));
+    HIPCHK(hipMemcpyAsync(&ws.h[0], a.rboff + n, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&ws.h[1], a.status, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    a.V = ws.h[0];
+    if ((int32_t)ws.h[1] & kAxtBadWindow)
+        return gac_fail(GAC_E_ARG, "gac_axt_cut: a range's chain index is out of range");
+    const size_t b_pidx = up16((size_t)(a.V + 2) * 8), b_part = up16((size_t)(a.V / 2048 + 2) * 8);
+    HIPCHK(arena_need(ws.a2, b_pidx + b_part, s));
+    a.pidx = (int64_t *)ws.a2.p;
+    a.part = (int64_t *)(ws.a2.p + b_pidx);
+    HIPCHK(launch_axt_cut_flag(a, s));
+    HIPCHK(hipMemcpyAsync(&ws.h[0], a.pidx + a.V, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&ws.h[1], a.status, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    a.P = ws.h[0];
+    if ((int32_t)ws.h[1] & kAxtBadGap) {
+        const int64_t r = ws.h[1] >> 32;
+        return gac_fail(GAC_E_FORMAT, "chain %d: negative gap between two blocks of range %lld "
+                                      "[%d, %d)", (int)ranges[r].chain, (long long)r,
+                        (int)ranges[r].t_start, (int)ranges[r].t_end);
+    }
+    // one allocation for the caller: the pieces, then first[0 .. n] (8-byte aligned)
+    const size_t b_pc = ((size_t)a.P * sizeof(Window) + 7) & ~(size_t)7;
+    HIPCHK(arena_need(ws.text, (size_t)a.P * sizeof(Window) + 16, s));
+    a.pieces = (Window *)ws.text.p;
+    char *res = (char *)malloc(b_pc + (size_t)(n + 1) * 8 + 8);
+    if (!res) return gac_fail(GAC_E_ARG, "gac_axt_cut: out of memory");
+    hipError_t e = launch_axt_cut_emit(a, s);
+    if (e == hipSuccess && a.P)
+        e = hipMemcpyAsync(res, a.pieces, (size_t)a.P * sizeof(Window), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(res + b_pc, a.first, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) {
+        free(res);
+        HIPCHK(e);
+    }
+    *pieces = (gac_window *)res;
+    *first = (int64_t *)(res + b_pc);
+    *n_pieces = a.P;
     return GAC_OK;
 }
 
@@ -3541,8 +3685,8 @@ extern "C" int gac_axt_job_open(gac_ctx *c, int64_t text_bytes, gac_axt_job **ou
     return GAC_OK;
 }
 
-extern "C" int gac_axt_job_submit(gac_axt_job *j, const gac_chainset *cs, const gac_window *pieces,
-                                  int64_t n, const int64_t *offsets, int64_t bytes) {
+static int axt_job_submit_x(gac_axt_job *j, const gac_chainset *cs, const gac_window *pieces,
+                            int64_t n, const int64_t *offsets, int64_t bytes, bool clip) {
     gac_clear_error();
     if (!j || !j->ctx) return gac_fail(GAC_E_ARG, "NULL or orphaned job");
     gac_ctx *c = j->ctx;
@@ -3555,11 +3699,23 @@ extern "C" int gac_axt_job_submit(gac_axt_job *j, const gac_chainset *cs, const 
     if (n == 0 || bytes == 0) return GAC_OK;
     int rc = job_text(j, bytes);
     if (rc != GAC_OK) return rc;
-    rc = axt_render_dev(c, cs, j->ws, pieces, nullptr, n, offsets, nullptr, j->ws.text.p, bytes, j->st);
+    rc = axt_render_dev(c, cs, j->ws, pieces, nullptr, n, offsets, nullptr, j->ws.text.p, bytes, clip,
+                        j->st);
     if (rc != GAC_OK) return rc;
     HIPCHK(hipMemcpyAsync(j->h_text, j->ws.text.p, (size_t)bytes, hipMemcpyDeviceToHost, j->st));
     j->bytes = bytes;
     return GAC_OK;
+}
+
+extern "C" int gac_axt_job_submit(gac_axt_job *j, const gac_chainset *cs, const gac_window *pieces,
+                                  int64_t n, const int64_t *offsets, int64_t bytes) {
+    return axt_job_submit_x(j, cs, pieces, n, offsets, bytes, false);
+}
+
+extern "C" int gac_axt_job_submit_clip(gac_axt_job *j, const gac_chainset *cs,
+                                       const gac_window *pieces, int64_t n, const int64_t *offsets,
+                                       int64_t bytes) {
+    return axt_job_submit_x(j, cs, pieces, n, offsets, bytes, true);
 }
 
 extern "C" int gac_axt_job_wait(gac_axt_job *j, const char **text, int64_t *bytes) {

@@ -267,12 +267,13 @@ struct ComposeArgs {
 };
 
 // k_axt_stat / k_axt_render (gac_axtout.hip): pieces (block windows of chains,
-// gac_window; t_start / t_end are not read) measured and written out as
+// gac_window; t_start / t_end are read in clip mode only) measured and written out as
 // alignment rows.  The pieces' blocks laid end to end are the call's virtual
 // blocks: pboff[p] = first virtual block of piece p, V = pboff[n].
 constexpr int kAxtBadWindow = 1;  // status[0] bits: a window outside its chain
 constexpr int kAxtBadGap = 2;     // a negative or double-sided gap inside a piece
 constexpr int kAxtBadOut = 4;     // a piece's rows outside the text buffer
+constexpr int kAxtBadClip = 8;    // clip mode: a piece's first or last block left empty
 struct AxtArgs {
     const uint2 *t_planes, *q_planes;
     const uint32_t *t_nmask, *q_nmask, *t_lmask, *q_lmask;
@@ -281,6 +282,8 @@ struct AxtArgs {
     int64_t n_chains;
     const Window *pieces;  // [n]
     int64_t n, V;
+    int32_t clip;          // host only: the launchers pick the kernels that read t_start / t_end
+                           // (netToAxt's clipped first and last block, chain.c:513-522)
     int64_t *pboff;        // [n + 1]
     int64_t *part;         // [max(n, V) / 2048 + 2] the scans' workgroup totals
     int32_t *status;       // [1] kAxtBad* bits (zeroed by the caller)
@@ -294,6 +297,25 @@ struct AxtArgs {
     int64_t *off;            // [n] the offsets used
     char *out;
     int64_t out_bytes;
+};
+
+// k_cut_* (gac_axtout.hip): ranges (chain, tStart, tEnd) to the clipped pieces
+// chainToAxt(chainSubsetOnT(...)) makes.  The ranges' selected blocks laid end
+// to end are the call's virtual blocks: rboff[r] = first of range r.
+struct AxtCutArgs {
+    const DChain *chains;
+    const int4 *blk;
+    int64_t n_chains;
+    const Range *ranges;  // [n]
+    int64_t n, V, P;      // ranges, virtual blocks, pieces
+    int32_t max_gap;
+    int32_t *rfirst;      // [n] chain-local first block of each range
+    int64_t *rboff;       // [n + 1]
+    int64_t *pidx;        // [V + 2] break flags, then their exclusive scan (pidx[V] = P)
+    int64_t *part;        // [max(n, V) / 2048 + 2]
+    int32_t *status;      // [0] kAxtBad* bits, [1] the lowest range with a negative gap
+    Window *pieces;       // [P]
+    int64_t *first;       // [n + 1]
 };
 
 }  // namespace gac

@@ -69,28 +69,6 @@ static double now_s(void) {
     return ts.tv_sec + 1e-9 * ts.tv_nsec;
 }
 
-/* v in decimal and one space; s and one space */
-static char *put_int(char *p, int64_t v) {
-    char d[24];
-    int n = 0;
-    uint64_t u = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
-    if (v < 0)
-        *p++ = '-';
-    do
-        d[n++] = (char)('0' + u % 10);
-    while ((u /= 10) != 0);
-    while (n)
-        *p++ = d[--n];
-    *p++ = ' ';
-    return p;
-}
-
-static char *put_str(char *p, const char *s, size_t n) {
-    memcpy(p, s, n);
-    p[n] = ' ';
-    return p + n + 1;
-}
-
 static size_t *name_lens(const gt_names *t) {
     size_t *len = malloc((size_t)(t->n ? t->n : 1) * sizeof(*len));
     if (!len)
@@ -279,16 +257,16 @@ int main(int argc, char *argv[]) {
                 const int32_t tn = c.tname[i], qn = c.qname[i];
                 if (tlen[tn] + qlen[qn] + 128 > sizeof head)
                     gt_abort("sequence names too long for an axt header line");
-                char *h = put_int(head, p);
-                h = put_str(h, c.tnames.names[tn], tlen[tn]);
-                h = put_int(h, (int64_t)pc[p].t_start + 1);
-                h = put_int(h, pc[p].t_end);
-                h = put_str(h, c.qnames.names[qn], qlen[qn]);
-                h = put_int(h, (int64_t)bq[b0] + 1);
-                h = put_int(h, (int64_t)bq[b1] + bs[b1]);
+                char *h = gt_put_int(head, p);
+                h = gt_put_str(h, c.tnames.names[tn], tlen[tn]);
+                h = gt_put_int(h, (int64_t)pc[p].t_start + 1);
+                h = gt_put_int(h, pc[p].t_end);
+                h = gt_put_str(h, c.qnames.names[qn], qlen[qn]);
+                h = gt_put_int(h, (int64_t)bq[b0] + 1);
+                h = gt_put_int(h, (int64_t)bq[b1] + bs[b1]);
                 *h++ = c.qstrand[i] ? '-' : '+';
                 *h++ = ' ';
-                h = put_int(h, score[p]);
+                h = gt_put_int(h, score[p]);
                 h[-1] = '\n';
                 fwrite(head, 1, (size_t)(h - head), out);
                 fwrite(text + off[p], 1, (size_t)(2 * sym[p] + 3), out);

@@ -279,6 +279,30 @@ typedef struct gt_sizes {
 void gt_read_sizes(const char *path, gt_sizes *s);
 void gt_sizes_free(gt_sizes *s);
 
+/* ---- axt header lines (axtWrite, kent/src/lib/axt.c:101-114), field by field
+ * into a caller's buffer: printf's format parsing was most of chainToAxt's time
+ * on a whole genome.  v in decimal and one space; s (n bytes) and one space. */
+static inline char *gt_put_int(char *p, int64_t v) {
+    char d[24];
+    int n = 0;
+    uint64_t u = v < 0 ? 0 - (uint64_t)v : (uint64_t)v;
+    if (v < 0)
+        *p++ = '-';
+    do
+        d[n++] = (char)('0' + u % 10);
+    while ((u /= 10) != 0);
+    while (n)
+        *p++ = d[--n];
+    *p++ = ' ';
+    return p;
+}
+
+static inline char *gt_put_str(char *p, const char *s, size_t n) {
+    __builtin_memcpy(p, s, n);
+    p[n] = ' ';
+    return p + n + 1;
+}
+
 FILE *gt_must_open(const char *path, const char *mode);
 /* whole file (".gz" decompressed, "stdin" allowed) into a NUL-terminated buffer */
 char *gt_slurp(const char *path, size_t *len);

@@ -204,41 +204,66 @@ class Engine:
             lib().gac_axt_free(p)
         return out
 
-    def axt_measure(self, cs: "ChainSet", pieces: np.ndarray):
-        """(score int32, match, ali, sym int64) of every piece (gac_axt_measure)."""
+    def axt_cut(self, cs: "ChainSet", ranges: np.ndarray, max_gap: int = 100):
+        """netToAxt's clipped pieces of sub-chain ranges (gac_axt_cut).  ranges:
+        int32 [n, 3] (chain, tStart, tEnd).  Returns (pieces int32 [P, 5] with
+        the clipped tStart / tEnd, first int64 [n + 1]): range r's pieces are
+        pieces[first[r]:first[r + 1]]."""
+        rg = np.ascontiguousarray(np.asarray(ranges, dtype=np.int32).reshape(-1, 3))
+        n = rg.shape[0]
+        p, f = C.c_void_p(), C.c_void_p()
+        m = C.c_int64()
+        check(lib().gac_axt_cut(self.h, cs.handle, _p(rg), n, int(max_gap), C.byref(p), C.byref(f),
+                                C.byref(m)))
+        try:
+            pieces = np.zeros((m.value, 5), np.int32)
+            first = np.zeros(n + 1, np.int64)
+            if m.value:
+                C.memmove(_p(pieces), p, m.value * 20)
+            C.memmove(_p(first), f, (n + 1) * 8)
+        finally:
+            lib().gac_axt_free(p)  # (one allocation: first goes with it)
+        return pieces, first
+
+    def axt_measure(self, cs: "ChainSet", pieces: np.ndarray, clip: bool = False):
+        """(score int32, match, ali, sym int64) of every piece (gac_axt_measure;
+        clip: gac_axt_measure_clip, which reads the pieces' tStart / tEnd)."""
         w = np.ascontiguousarray(np.asarray(pieces, dtype=np.int32).reshape(-1, 5))
         n = w.shape[0]
         score = np.zeros(n, np.int32)
         match, ali, sym = (np.zeros(n, np.int64) for _ in range(3))
-        check(lib().gac_axt_measure(self.h, cs.handle, _p(w), n, _p(score), _p(match), _p(ali),
-                                    _p(sym)))
+        fn = lib().gac_axt_measure_clip if clip else lib().gac_axt_measure
+        check(fn(self.h, cs.handle, _p(w), n, _p(score), _p(match), _p(ali), _p(sym)))
         return score, match, ali, sym
 
     def axt_measure_device(self, cs: "ChainSet", d_pieces: int, n: int, d_score: int, d_match: int,
-                           d_ali: int, d_sym: int, stream: int = 0) -> None:
-        check(lib().gac_axt_measure_device(
+                           d_ali: int, d_sym: int, stream: int = 0, clip: bool = False) -> None:
+        fn = lib().gac_axt_measure_clip_device if clip else lib().gac_axt_measure_device
+        check(fn(
             self.h, cs.handle, C.c_void_p(d_pieces), n, C.c_void_p(d_score), C.c_void_p(d_match),
             C.c_void_p(d_ali), C.c_void_p(d_sym), C.c_void_p(stream) if stream else None))
 
     def axt_render(self, cs: "ChainSet", pieces: np.ndarray, offsets=None, out=None,
-                   sym=None) -> np.ndarray:
+                   sym=None, clip: bool = False) -> np.ndarray:
         """The pieces' rows, tSym '\\n' qSym '\\n' '\\n' each (gac_axt_render), into
         the uint8 array `out` at byte `offsets` [n]; both None: packed in order
-        into a new array (sym: the pieces' column counts, measured if None)."""
+        into a new array (sym: the pieces' column counts, measured if None).
+        clip: gac_axt_render_clip, which reads the pieces' tStart / tEnd."""
         w = np.ascontiguousarray(np.asarray(pieces, dtype=np.int32).reshape(-1, 5))
         n = w.shape[0]
         if out is None:
             if sym is None:
-                sym = self.axt_measure(cs, w)[3]
+                sym = self.axt_measure(cs, w, clip=clip)[3]
             out = np.zeros(int((2 * np.asarray(sym, np.int64) + 3).sum()), np.uint8)
         off = None if offsets is None else np.ascontiguousarray(offsets, np.int64)
-        check(lib().gac_axt_render(self.h, cs.handle, _p(w), n, _p(off) if off is not None else None,
-                                   _p(out), out.size))
+        fn = lib().gac_axt_render_clip if clip else lib().gac_axt_render
+        check(fn(self.h, cs.handle, _p(w), n, _p(off) if off is not None else None, _p(out), out.size))
         return out
 
     def axt_render_device(self, cs: "ChainSet", d_pieces: int, n: int, d_offsets: int, d_out: int,
-                          out_bytes: int, stream: int = 0) -> None:
-        check(lib().gac_axt_render_device(
+                          out_bytes: int, stream: int = 0, clip: bool = False) -> None:
+        fn = lib().gac_axt_render_clip_device if clip else lib().gac_axt_render_device
+        check(fn(
             self.h, cs.handle, C.c_void_p(d_pieces), n, C.c_void_p(d_offsets) if d_offsets else None,
             C.c_void_p(d_out), out_bytes, C.c_void_p(stream) if stream else None))
 

@@ -36,6 +36,11 @@
  *                          + axtIdRatio           kent/src/hg/mouseStuff/chainToAxt/chainToAxt.c:69-89
  *   gac_axt_render        <- loadSeqStrand        kent/src/hg/mouseStuff/chainToAxt/chainToAxt.c:48-67
  *                          + axtFromBlocks        kent/src/lib/chainToAxt.c:14-91
+ *   gac_axt_cut           <- chainSubsetOnT       kent/src/lib/chain.c:471-558
+ *                          + chainToAxt           kent/src/lib/chainToAxt.c:93-124
+ *   gac_axt_*_clip        <- chainFastSubsetOnT's clipped first and last block
+ *                                                 kent/src/lib/chain.c:513-522
+ *                          (writeChainPart, kent/src/hg/mouseStuff/netToAxt/netToAxt.c:76-105)
  */
 #ifndef GACHAIN_H
 #define GACHAIN_H
@@ -51,8 +56,9 @@ extern "C" {
 #define GAC_ABI_VERSION 1
 /* Bumped when entry points are added and nothing existing changes (a caller
  * built against minor m runs with any library of minor >= m):
- * 1 = the alignment text entry points (gac_axt_*). */
-#define GAC_ABI_MINOR 1
+ * 1 = the alignment text entry points (gac_axt_*).
+ * 2 = gac_axt_cut and the clip-aware gac_axt_*_clip entry points (netToAxt). */
+#define GAC_ABI_MINOR 2
 
 /* return codes */
 #define GAC_OK 0
@@ -310,9 +316,10 @@ int gac_antirepeat_pass(double score, const int64_t match[4], int64_t rep, int64
 /* ---- alignment text (chainToAxt) ------------------------------------------
  * A piece is a window of consecutive blocks of one chain (gac_window: chain,
  * first_block, n_blocks; t_start / t_end are informative and not read) that
- * becomes one axt record.  The entry points take any block windows, so
- * sub-chains of net fills can be fed later; a window holding a negative or
- * double-sided gap is GAC_E_ARG.
+ * becomes one axt record.  The entry points take any block windows; the
+ * sub-chains of net fills, whose first and last block are clipped, go through
+ * gac_axt_cut and the _clip forms further down.  A window holding a negative
+ * or double-sided gap is GAC_E_ARG.
  *
  * gac_axt_split cuts every chain of a parsed set where chainToAxt() does
  * (kent/src/lib/chainToAxt.c:105-121, called with maxChain = BIGNUM as
@@ -376,6 +383,50 @@ int gac_axt_job_submit(gac_axt_job *job, const gac_chainset *cs, const gac_windo
                        int64_t n, const int64_t *offsets, int64_t bytes);
 int gac_axt_job_wait(gac_axt_job *job, const char **text, int64_t *bytes);
 void gac_axt_job_close(gac_axt_job *job);
+
+/* ---- sub-chains of net fills (netToAxt) -----------------------------------
+ * For range r, the pieces chainToAxt(chainSubsetOnT(chain, t_start, t_end),
+ * max_gap, BIGNUM) makes (kent/src/lib/chain.c:471-558, kent/src/lib/
+ * chainToAxt.c:93-124; writeChainPart, kent/src/hg/mouseStuff/netToAxt/
+ * netToAxt.c:76-105), in order: (*pieces)[(*first)[r] .. (*first)[r + 1]).  A
+ * piece's first_block / n_blocks are chain-local; its t_start / t_end are the
+ * clipped target span (max(first block's tStart, r.t_start), min(last block's
+ * tEnd, r.t_end)), so only a range's first piece can have a cut head and only
+ * its last a cut tail.  A range that selects no block (t_start >= t_end
+ * included) gives no piece: first[r] == first[r + 1] (the reference's "null
+ * subchain").  first has n + 1 entries, first[n] == *n_pieces.
+ * Everything runs on the device, cut over the selected blocks: a range costs
+ * two binary searches plus what its blocks cost.  Host buffers, synchronous.
+ * *pieces and *first are ONE allocation: release both with gac_axt_free(*pieces)
+ * and never free *first.  A chain index out of range, or a NULL or orphaned
+ * set, is GAC_E_ARG; a negative dq or dt between two blocks of a selected
+ * window is GAC_E_FORMAT and gac_last_error names a chain (by its index in the
+ * set) it happened in, as gac_axt_split does.  On error *pieces and *first are
+ * NULL. */
+int gac_axt_cut(gac_ctx *ctx, const gac_chainset *cs, const gac_range *ranges, int64_t n,
+                int32_t max_gap, gac_window **pieces, int64_t **first, int64_t *n_pieces);
+/* gac_axt_measure / gac_axt_render / their _device forms / gac_axt_job_submit
+ * with the same arguments and results, but t_start / t_end are read
+ * (chainFastSubsetOnT, chain.c:513-522): a piece's first block starts at
+ * max(tStart, t_start), its last block ends at min(tEnd, t_end), the query
+ * following (qStart += cut head, qEnd -= cut tail); for a one-block piece both
+ * cuts apply to that block.  Inner gaps are never touched.  A piece whose first
+ * or last block is left empty by its clip is GAC_E_ARG, found before anything
+ * is written.  A piece whose t_start / t_end equal its blocks' span (every
+ * piece of gac_axt_split) gives exactly what the unclipped entry points give;
+ * those go on ignoring the two fields. */
+int gac_axt_measure_clip(gac_ctx *ctx, const gac_chainset *cs, const gac_window *pieces, int64_t n,
+                         int32_t *score, int64_t *match, int64_t *ali, int64_t *sym);
+int gac_axt_measure_clip_device(gac_ctx *ctx, const gac_chainset *cs, const gac_window *d_pieces,
+                                int64_t n, int32_t *d_score, int64_t *d_match, int64_t *d_ali,
+                                int64_t *d_sym, void *stream);
+int gac_axt_render_clip(gac_ctx *ctx, const gac_chainset *cs, const gac_window *pieces, int64_t n,
+                        const int64_t *offsets, char *out, int64_t out_bytes);
+int gac_axt_render_clip_device(gac_ctx *ctx, const gac_chainset *cs, const gac_window *d_pieces,
+                               int64_t n, const int64_t *d_offsets, char *d_out, int64_t out_bytes,
+                               void *stream);
+int gac_axt_job_submit_clip(gac_axt_job *job, const gac_chainset *cs, const gac_window *pieces,
+                            int64_t n, const int64_t *offsets, int64_t bytes);
 
 /* ---- caller text (the kent in-process API's char* entry points) ---------
  * chainScoreBlock / axtScoreUngapped (kent/src/lib/chainConnect.c:14-22,
