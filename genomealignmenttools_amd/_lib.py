@@ -153,6 +153,9 @@ _PROTOS = {
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gac_chain_composition_device": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gac_chain_psl_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gac_chain_psl_counts_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gac_antirepeat_pass": (
         C.c_int, [C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int]),
     "gac_abi_minor": (C.c_int, []),

@@ -1,7 +1,12 @@
-// gac_compose.hip -- per-chain match composition of an uploaded chain set
-// (gac_chain_composition; chainAntiRepeat's degeneracyFilter / repeatFilter
-// counts, kent/src/hg/mouseStuff/chainAntiRepeat/chainAntiRepeat.c:53-66,
-// 102-114).  gfx950 only.
+// gac_compose.hip -- per-chain base counts of an uploaded chain set: one walk
+// over the aligned bases (chain_walk), instantiated with a counting policy as
+//   k_compose     gac_chain_composition: chainAntiRepeat's degeneracyFilter /
+//                 repeatFilter counts (kent/src/hg/mouseStuff/chainAntiRepeat/
+//                 chainAntiRepeat.c:53-66, 102-114)
+//   k_psl_counts  gac_chain_psl_counts: chainToPsl's match / misMatch /
+//                 repMatch / nCount (kent/src/hg/mouseStuff/chainToPsl/
+//                 chainToPsl.c:106-131)
+// gfx950 only.
 //
 // Work is cut as k_tile cuts it: a wave takes a tile of 64 consecutive blocks
 // of the flat block array (whatever chains they belong to), one block per
@@ -13,6 +18,11 @@
 // add to the workgroup's per-chain slots in LDS (chain boundaries inside 64
 // chunks); each workgroup then issues one global atomicAdd per counter for
 // every chain it met.  Integer sums: any order gives the same result.
+//
+// A policy P names its kernel arguments (Args, a ChainWalkArgs), the number of
+// sums it keeps per chain (kVals), whether it reads the query's soft-mask
+// plane (kQLower), what a chunk of up to 32 aligned bases adds to the sums
+// (count) and where a workgroup's sums of one chain go (emit).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -23,7 +33,6 @@ namespace gac {
 namespace {
 
 constexpr int kCompSlots = kWavesPerWG * kTileBlocks;  // blocks (so chains at most) per workgroup
-constexpr int kCompVals = 6;                           // match[4], rep, total
 
 typedef uint32_t cu32x4a8 __attribute__((ext_vector_type(4), aligned(8)));
 typedef uint32_t cu32x2a4 __attribute__((ext_vector_type(2), aligned(4)));
@@ -57,15 +66,16 @@ struct CompWave {
 // wave; `want`: this lane's chain changes now.  When every lane holding sums
 // holds them for one chain the wave folds them first (one LDS add per
 // counter); otherwise the lanes that change chain add their own.
-__device__ __forceinline__ void comp_flush(unsigned long long (*acc)[kCompVals], int lane,
-                                           int &cur, uint32_t (&v)[kCompVals], bool want) {
+template <int kVals>
+__device__ __forceinline__ void comp_flush(unsigned long long (*acc)[kVals], int lane, int &cur,
+                                           uint32_t (&v)[kVals], bool want) {
     const bool have = cur >= 0;
     if (!__ballot(want && have)) return;
     const unsigned long long hm = __ballot(have);
     const int u = __shfl(cur, (int)__builtin_ctzll(hm), kWave);
     if (!__ballot(have && cur != u)) {
 #pragma unroll
-        for (int k = 0; k < kCompVals; ++k) {
+        for (int k = 0; k < kVals; ++k) {
             unsigned long long s = have ? v[k] : 0u;
 #pragma unroll
             for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, kWave);
@@ -75,7 +85,7 @@ __device__ __forceinline__ void comp_flush(unsigned long long (*acc)[kCompVals],
         cur = -1;
     } else if (want && have) {
 #pragma unroll
-        for (int k = 0; k < kCompVals; ++k) {
+        for (int k = 0; k < kVals; ++k) {
             if (v[k]) atomicAdd(&acc[cur][k], (unsigned long long)v[k]);
             v[k] = 0;
         }
@@ -83,13 +93,66 @@ __device__ __forceinline__ void comp_flush(unsigned long long (*acc)[kCompVals],
     }
 }
 
-__global__ void __launch_bounds__(256) k_compose(ComposeArgs a) {
+// chainAntiRepeat: matches by nucleotide, positions lower-case on either
+// side, aligned bases
+struct ComposePolicy {
+    typedef ComposeArgs Args;
+    static constexpr int kVals = 6;  // match[4], rep, total
+    static constexpr bool kQLower = true;
+    // t0 / t1: the target's code planes; eq: equal bases (N on neither side);
+    // nn: N on either side; tl / ql: lower case; in: the chunk's n valid bits
+    static __device__ __forceinline__ void count(uint32_t (&v)[kVals], uint32_t t0, uint32_t t1,
+                                                 uint32_t eq, uint32_t nn, uint32_t tl, uint32_t ql,
+                                                 uint32_t in, int n) {
+        v[0] += (uint32_t)__builtin_popcount(eq & ~t0 & ~t1);  // T
+        v[1] += (uint32_t)__builtin_popcount(eq & t0 & ~t1);   // C
+        v[2] += (uint32_t)__builtin_popcount(eq & ~t0 & t1);   // A
+        v[3] += (uint32_t)__builtin_popcount(eq & t0 & t1);    // G
+        v[4] += (uint32_t)__builtin_popcount((tl | ql) & in);
+        v[5] += (uint32_t)n;
+    }
+    static __device__ __forceinline__ void emit(const Args &a, int c, const unsigned long long *s) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (s[k]) atomicAdd(&a.match[(int64_t)c * 4 + k], s[k]);
+        if (s[4]) atomicAdd(&a.rep[c], s[4]);
+        if (s[5]) atomicAdd(&a.total[c], s[5]);
+    }
+};
+
+// chainToPsl (chainToPsl.c:106-124): N on either side first, then equal bases
+// by the target's case, the rest mismatches; the query's case is not read
+struct PslPolicy {
+    typedef PslArgs Args;
+    static constexpr int kVals = 4;  // match, repMatch, nCount, aligned bases
+    static constexpr bool kQLower = false;
+    static __device__ __forceinline__ void count(uint32_t (&v)[kVals], uint32_t, uint32_t,
+                                                 uint32_t eq, uint32_t nn, uint32_t tl, uint32_t,
+                                                 uint32_t, int n) {
+        v[0] += (uint32_t)__builtin_popcount(eq & ~tl);
+        v[1] += (uint32_t)__builtin_popcount(eq & tl);
+        v[2] += (uint32_t)__builtin_popcount(nn);
+        v[3] += (uint32_t)n;
+    }
+    static __device__ __forceinline__ void emit(const Args &a, int c, const unsigned long long *s) {
+        unsigned long long *o = a.counts + (int64_t)c * 4;  // match, misMatch, repMatch, nCount
+        const unsigned long long mis = s[3] - s[0] - s[1] - s[2];
+        if (s[0]) atomicAdd(&o[0], s[0]);
+        if (mis) atomicAdd(&o[1], mis);
+        if (s[1]) atomicAdd(&o[2], s[1]);
+        if (s[2]) atomicAdd(&o[3], s[2]);
+    }
+};
+
+template <class P>
+__device__ __forceinline__ void chain_walk(const typename P::Args &a) {
+    constexpr int kVals = P::kVals;
     __shared__ CompWave s_w[kWavesPerWG];
-    __shared__ unsigned long long s_acc[kCompSlots][kCompVals];
+    __shared__ unsigned long long s_acc[kCompSlots][kVals];
     __shared__ int s_chain[kCompSlots];
     const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < kCompVals; ++k) s_acc[threadIdx.x][k] = 0ull;
+    for (int k = 0; k < kVals; ++k) s_acc[threadIdx.x][k] = 0ull;
     s_chain[threadIdx.x] = -1;
     __syncthreads();
     const int64_t B0 = (int64_t)blockIdx.x * kCompSlots;
@@ -136,7 +199,7 @@ __global__ void __launch_bounds__(256) k_compose(ComposeArgs a) {
         comp_wave_sync();
 
         int cur = -1;
-        uint32_t v[kCompVals] = {0, 0, 0, 0, 0, 0};
+        uint32_t v[kVals] = {};
         for (int c0 = 0; c0 < C; c0 += kWave) {
             const int j = c0 + lane;
             const bool on = j < C;
@@ -162,7 +225,8 @@ __global__ void __launch_bounds__(256) k_compose(ComposeArgs a) {
                 const cu32x4a8 tv = *reinterpret_cast<const cu32x4a8 *>(a.t_planes + tw);
                 const cu32x4a8 qv = *reinterpret_cast<const cu32x4a8 *>(a.q_planes + qw);
                 const uint32_t tl = mask_window(a.t_lmask, tw, sht);
-                uint32_t ql = mask_window(a.q_lmask, qw, shq);
+                uint32_t ql = 0;
+                if (P::kQLower) ql = mask_window(a.q_lmask, qw, shq);
                 uint32_t nm = 0, qn = 0;
                 if (lq & kTHasN) nm = mask_window(a.t_nmask, tw, sht);
                 if (lq & kQHasN) qn = mask_window(a.q_nmask, qw, shq);
@@ -178,12 +242,7 @@ __global__ void __launch_bounds__(256) k_compose(ComposeArgs a) {
                 }
                 const uint32_t in = n >= 32 ? 0xffffffffu : ((1u << n) - 1u);
                 const uint32_t eq = ~((t0 ^ q0) | (t1 ^ q1)) & ~(nm | qn) & in;
-                v[0] += (uint32_t)__builtin_popcount(eq & ~t0 & ~t1);  // T
-                v[1] += (uint32_t)__builtin_popcount(eq & t0 & ~t1);   // C
-                v[2] += (uint32_t)__builtin_popcount(eq & ~t0 & t1);   // A
-                v[3] += (uint32_t)__builtin_popcount(eq & t0 & t1);    // G
-                v[4] += (uint32_t)__builtin_popcount((tl | ql) & in);
-                v[5] += (uint32_t)n;
+                P::count(v, t0, t1, eq, (nm | qn) & in, tl, ql, in, n);
                 cur = sl;
             }
         }
@@ -191,15 +250,12 @@ __global__ void __launch_bounds__(256) k_compose(ComposeArgs a) {
     }
     __syncthreads();
     const int c = s_chain[threadIdx.x];
-    if (c >= 0) {  // one add per (workgroup, chain, counter)
-        const unsigned long long *s = s_acc[threadIdx.x];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (s[k]) atomicAdd(&a.match[(int64_t)c * 4 + k], s[k]);
-        if (s[4]) atomicAdd(&a.rep[c], s[4]);
-        if (s[5]) atomicAdd(&a.total[c], s[5]);
-    }
+    if (c >= 0) P::emit(a, c, s_acc[threadIdx.x]);  // one add per (workgroup, chain, counter)
 }
+
+__global__ void __launch_bounds__(256) k_compose(ComposeArgs a) { chain_walk<ComposePolicy>(a); }
+
+__global__ void __launch_bounds__(256) k_psl_counts(PslArgs a) { chain_walk<PslPolicy>(a); }
 
 }  // namespace
 
@@ -207,6 +263,13 @@ hipError_t launch_compose(const ComposeArgs &a, hipStream_t s) {
     const int64_t g = (a.ntiles + kWavesPerWG - 1) / kWavesPerWG;
     if (g <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_compose, dim3((unsigned)g), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_psl_counts(const PslArgs &a, hipStream_t s) {
+    const int64_t g = (a.ntiles + kWavesPerWG - 1) / kWavesPerWG;
+    if (g <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_psl_counts, dim3((unsigned)g), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

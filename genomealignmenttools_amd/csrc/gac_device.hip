@@ -90,6 +90,7 @@ hipError_t launch_text_blocks(const uint8_t *text, const TextJob *jobs, int64_t 
 hipError_t launch_text_xover(const uint8_t *text, const TextXJob *jobs, int64_t n, const M25 &m,
                              int32_t *pos, int32_t *adj, hipStream_t s);
 hipError_t launch_compose(const ComposeArgs &a, hipStream_t s);
+hipError_t launch_psl_counts(const PslArgs &a, hipStream_t s);
 hipError_t launch_axt_plan(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_stat(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_place(const AxtArgs &a, hipStream_t s);
@@ -3137,6 +3138,22 @@ extern "C" int gac_score_chains(gac_ctx *c, const gac_chainset *cs, uint32_t fla
 // ------------------------------------------------------ match composition
 // (chainAntiRepeat; k_compose reads the set as the upload left it: no
 // scoring setup, no workspace)
+static void chain_walk_args(const gac_ctx *c, const gac_chainset *cs, ChainWalkArgs &a) {
+    a.t_planes = c->g[0].planes;
+    a.q_planes = c->g[1].planes;
+    a.t_nmask = c->g[0].nmask;
+    a.q_nmask = c->g[1].nmask;
+    a.t_lmask = c->g[0].lmask;
+    a.q_lmask = c->g[1].lmask;
+    a.chains = cs->chains;
+    a.blk = cs->blk;
+    a.coff = cs->d_coff;
+    a.tile_c0 = cs->d_tile_c0;
+    a.n_chains = cs->n_chains;
+    a.n_blocks = cs->n_blocks;
+    a.ntiles = (cs->n_blocks + 63) >> 6;
+}
+
 static int compose_device(gac_ctx *c, const gac_chainset *cs, int64_t *d_match, int64_t *d_rep,
                           int64_t *d_total, hipStream_t s) {
     if (!c->g[0].final || !c->g[1].final || !c->g[0].lmask || !c->g[1].lmask)
@@ -3149,19 +3166,7 @@ static int compose_device(gac_ctx *c, const gac_chainset *cs, int64_t *d_match, 
     HIPCHK(hipMemsetAsync(d_rep, 0, (size_t)n * 8, s));
     HIPCHK(hipMemsetAsync(d_total, 0, (size_t)n * 8, s));
     ComposeArgs a;
-    a.t_planes = c->g[0].planes;
-    a.q_planes = c->g[1].planes;
-    a.t_nmask = c->g[0].nmask;
-    a.q_nmask = c->g[1].nmask;
-    a.t_lmask = c->g[0].lmask;
-    a.q_lmask = c->g[1].lmask;
-    a.chains = cs->chains;
-    a.blk = cs->blk;
-    a.coff = cs->d_coff;
-    a.tile_c0 = cs->d_tile_c0;
-    a.n_chains = n;
-    a.n_blocks = cs->n_blocks;
-    a.ntiles = (cs->n_blocks + 63) >> 6;
+    chain_walk_args(c, cs, a);
     a.match = (unsigned long long *)d_match;
     a.rep = (unsigned long long *)d_rep;
     a.total = (unsigned long long *)d_total;
@@ -3204,6 +3209,59 @@ extern "C" int gac_chain_composition(gac_ctx *c, const gac_chainset *cs, int64_t
     if (d) hipFree(d);
     if (rc == GAC_OK && e != hipSuccess)
         return gac_fail(GAC_E_HIP, "gac_chain_composition failed: %s", hipGetErrorString(e));
+    return rc;
+}
+
+// ------------------------------------------------------ PSL match counts
+// (chainToPsl, chainToPsl.c:106-131; k_psl_counts walks the set as k_compose
+// does and reads the target's soft-mask plane only)
+static int psl_counts_device(gac_ctx *c, const gac_chainset *cs, int64_t *d_counts, hipStream_t s) {
+    if (!c->g[0].final || !c->g[1].final || !c->g[0].lmask)
+        return gac_fail(GAC_E_STATE, "gac_chain_psl_counts: the target side needs the soft-mask "
+                                     "plane (gac_genome_want_softmask before loading)");
+    const int64_t n = cs->n_chains;
+    if (n == 0) return GAC_OK;
+    if (!d_counts) return gac_fail(GAC_E_ARG, "NULL buffer");
+    HIPCHK(hipMemsetAsync(d_counts, 0, (size_t)n * 4 * 8, s));
+    PslArgs a;
+    chain_walk_args(c, cs, a);
+    a.counts = (unsigned long long *)d_counts;
+    HIPCHK(launch_psl_counts(a, s));
+    return GAC_OK;
+}
+
+extern "C" int gac_chain_psl_counts_device(gac_ctx *c, const gac_chainset *cs, int64_t *d_counts,
+                                           void *stream) {
+    gac_clear_error();
+    if (!c) return gac_fail(GAC_E_ARG, "NULL context");
+    if (!cs || cs->ctx != c) return gac_fail(GAC_E_ARG, "NULL or orphaned chainset");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    return psl_counts_device(c, cs, d_counts, stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int gac_chain_psl_counts(gac_ctx *c, const gac_chainset *cs, int64_t *counts) {
+    gac_clear_error();
+    if (!c) return gac_fail(GAC_E_ARG, "NULL context");
+    if (!cs || cs->ctx != c) return gac_fail(GAC_E_ARG, "NULL or orphaned chainset");
+    CTX_LOCK(c);
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t n = cs->n_chains;
+    int64_t *d = nullptr;
+    if (n) {
+        if (!counts) return gac_fail(GAC_E_ARG, "NULL buffer");
+        HIPCHK(hipMalloc(&d, (size_t)n * 4 * 8));
+    }
+    hipStream_t s = c->stream;
+    int rc = psl_counts_device(c, cs, d, s);
+    hipError_t e = hipSuccess;
+    if (rc == GAC_OK && n) {
+        e = hipMemcpyAsync(counts, d, (size_t)n * 4 * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (d) hipFree(d);
+    if (rc == GAC_OK && e != hipSuccess)
+        return gac_fail(GAC_E_HIP, "gac_chain_psl_counts failed: %s", hipGetErrorString(e));
     return rc;
 }
 

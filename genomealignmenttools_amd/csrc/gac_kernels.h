@@ -250,20 +250,30 @@ struct M25 {  // score by text code, [q * 5 + t]; code 4 (not acgt) scores 0
     int32_t m[25];
 };
 
-// k_compose (gac_compose.hip): per-chain match composition of an uploaded
-// set.  lmask[w]: the opt-in soft-mask plane of a genome side, indexed like
-// nmask -- bit i set = base 32w+i lies in a .2bit mask run (lower case with
-// twoBitReadSeqFragExt's doMask); padding words and tail bits are 0.
-struct ComposeArgs {
+// The per-chain base counts of an uploaded set (gac_compose.hip): what the
+// walk over the aligned bases reads.  lmask[w]: the opt-in soft-mask plane of
+// a genome side, indexed like nmask -- bit i set = base 32w+i lies in a .2bit
+// mask run (lower case with twoBitReadSeqFragExt's doMask); padding words and
+// tail bits are 0.
+struct ChainWalkArgs {
     const uint2 *t_planes, *q_planes;
     const uint32_t *t_nmask, *q_nmask, *t_lmask, *q_lmask;
     const DChain *chains;
     const int4 *blk;
     const int32_t *coff, *tile_c0;  // the chain set's compact offsets / tile chains
     int64_t n_chains, n_blocks, ntiles;
+};
+
+// k_compose: chainAntiRepeat's match composition
+struct ComposeArgs : ChainWalkArgs {
     unsigned long long *match;  // [n_chains][4] by code T, C, A, G (zeroed by the caller)
     unsigned long long *rep;    // [n_chains]
     unsigned long long *total;  // [n_chains]
+};
+
+// k_psl_counts: chainToPsl's counts; q_lmask is not read (may be NULL)
+struct PslArgs : ChainWalkArgs {
+    unsigned long long *counts;  // [n_chains][4] match, misMatch, repMatch, nCount (zeroed by the caller)
 };
 
 // k_axt_stat / k_axt_render (gac_axtout.hip): pieces (block windows of chains,

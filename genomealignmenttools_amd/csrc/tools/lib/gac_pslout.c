@@ -1,0 +1,79 @@
+/* gac_pslout.c -- see gac_pslout.h */
+#include "gac_pslout.h"
+
+#include <stdlib.h>
+#include <string.h>
+
+/* v in decimal and one separator; u32: as "%u" of the 32-bit value, else "%d" */
+static inline char *put(char *p, int64_t v, int u32, char sep) {
+    p = gt_put_int(p, u32 ? (int64_t)(uint32_t)v : (int64_t)(int32_t)(uint32_t)v);
+    p[-1] = sep;
+    return p;
+}
+
+/* one of the three block lists: every element and a comma, then `end` */
+static char *put_list(FILE *f, char *buf, size_t cap, char *p, const int32_t *v, int64_t n,
+                      int u32, char end) {
+    for (int64_t b = 0; b < n; ++b) {
+        if ((size_t)(p - buf) > cap - 32) {
+            fwrite(buf, 1, (size_t)(p - buf), f);
+            p = buf;
+        }
+        p = put(p, v[b], u32, ',');
+    }
+    *p++ = end;
+    return p;
+}
+
+void gt_write_psl(FILE *f, const gt_chains *c, int64_t i, const int64_t counts[4], int basic) {
+    const int64_t b0 = c->blk_off[i], nb = c->blk_off[i + 1] - b0;
+    const int32_t *bt = c->bt + b0, *bq = c->bq + b0, *bs = c->bs + b0;
+    uint32_t qn = 0, qb = 0, tn = 0, tb = 0; /* the reference's ints: 32-bit sums */
+    for (int64_t b = 0; b + 1 < nb; ++b) {
+        const int32_t dq = bq[b + 1] - (bq[b] + bs[b]), dt = bt[b + 1] - (bt[b] + bs[b]);
+        if (basic ? dq > 0 : dq != 0) {
+            ++qn;
+            qb += (uint32_t)dq;
+        }
+        if (basic ? dt > 0 : dt != 0) {
+            ++tn;
+            tb += (uint32_t)dt;
+        }
+    }
+    const char *tname = c->tnames.names[c->tname[i]], *qname = c->qnames.names[c->qname[i]];
+    const size_t tl = strlen(tname), ql = strlen(qname);
+    const size_t cap = 1 << 14, need = tl + ql + 512;
+    char small[1 << 14], *buf = need <= cap ? small : malloc(need), *p = buf;
+    if (!buf)
+        gt_abort("Out of memory");
+    for (int k = 0; k < 4; ++k)
+        p = put(p, counts[k], basic, '\t');
+    p = put(p, qn, basic, '\t');
+    p = put(p, qb, 0, '\t');
+    p = put(p, tn, basic, '\t');
+    p = put(p, tb, 0, '\t');
+    *p++ = c->qstrand[i] ? '-' : '+';
+    *p++ = '\t';
+    memcpy(p, qname, ql);
+    p += ql;
+    *p++ = '\t';
+    p = put(p, c->qsize[i], basic, '\t');
+    p = put(p, c->qstrand[i] ? (int64_t)c->qsize[i] - c->qend[i] : c->qstart[i], basic, '\t');
+    p = put(p, c->qstrand[i] ? (int64_t)c->qsize[i] - c->qstart[i] : c->qend[i], basic, '\t');
+    memcpy(p, tname, tl);
+    p += tl;
+    *p++ = '\t';
+    p = put(p, c->tsize[i], basic, '\t');
+    p = put(p, c->tstart[i], basic, '\t');
+    p = put(p, c->tend[i], basic, '\t');
+    p = put(p, nb, basic, '\t');
+    if (buf != small) { /* a long name: the lists go through the small buffer */
+        fwrite(buf, 1, (size_t)(p - buf), f);
+        free(buf);
+        buf = p = small;
+    }
+    p = put_list(f, buf, cap, p, bs, nb, basic, '\t');
+    p = put_list(f, buf, cap, p, bq, nb, basic, '\t');
+    p = put_list(f, buf, cap, p, bt, nb, basic, '\n');
+    fwrite(buf, 1, (size_t)(p - buf), f);
+}

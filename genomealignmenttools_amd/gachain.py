@@ -12,6 +12,7 @@ scoreChain getChainScore (scoreChain.c:207)  Engine.score_chains(chainset) (gac_
 twoBitReadSeqFragExt(doMask) (twoBit.c:835)  Engine.load_2bit(..., soft_mask=True), decode_case
 chainAntiRepeat's two filters' counts        Engine.chain_composition(chainset)
   (chainAntiRepeat.c:40-117) and decision    antirepeat_pass(score, match, rep, total, minScore)
+chainToPsl's four counts (chainToPsl.c:106)  Engine.chain_psl_counts(chainset)
 axtScoreUngapped per block (axt.c:186-194)   Engine.score_blocks / score_text_blocks (caller text)
 cBlockFindCrossover (chainConnect.c:61-105)  Engine.crossovers / text_crossovers (caller text)
 chainBlocks' kd-tree DP (chainBlock.c:400)   Engine.chain_dp_blocks (total, predecessor per block)
@@ -184,6 +185,18 @@ class Engine:
         check(lib().gac_chain_composition_device(
             self.h, cs.handle, C.c_void_p(d_match), C.c_void_p(d_rep), C.c_void_p(d_total),
             C.c_void_p(stream) if stream else None))
+
+    def chain_psl_counts(self, cs: "ChainSet") -> np.ndarray:
+        """chainToPsl's counts of every chain of the set (gac_chain_psl_counts):
+        int64 [n, 4], columns match, misMatch, repMatch, nCount.  The target
+        side must hold the soft-mask plane; '-' block coordinates unshifted."""
+        counts = np.zeros((cs.n_chains, 4), np.int64)
+        check(lib().gac_chain_psl_counts(self.h, cs.handle, _p(counts)))
+        return counts
+
+    def chain_psl_counts_device(self, cs: "ChainSet", d_counts: int, stream: int = 0) -> None:
+        check(lib().gac_chain_psl_counts_device(
+            self.h, cs.handle, C.c_void_p(d_counts), C.c_void_p(stream) if stream else None))
 
     # ---- alignment text (chainToAxt)
     @staticmethod

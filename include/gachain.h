@@ -57,8 +57,9 @@ extern "C" {
 /* Bumped when entry points are added and nothing existing changes (a caller
  * built against minor m runs with any library of minor >= m):
  * 1 = the alignment text entry points (gac_axt_*).
- * 2 = gac_axt_cut and the clip-aware gac_axt_*_clip entry points (netToAxt). */
-#define GAC_ABI_MINOR 2
+ * 2 = gac_axt_cut and the clip-aware gac_axt_*_clip entry points (netToAxt).
+ * 3 = gac_chain_psl_counts[_device] (chainToPsl). */
+#define GAC_ABI_MINOR 3
 
 /* return codes */
 #define GAC_OK 0
@@ -312,6 +313,28 @@ int gac_chain_composition_device(gac_ctx *ctx, const gac_chainset *cs, int64_t *
  * (0/0 = NaN) is dropped as there.  1 = keep, 0 = drop.  Host only. */
 int gac_antirepeat_pass(double score, const int64_t match[4], int64_t rep, int64_t total,
                         int min_score);
+
+/* ---- PSL match counts (chainToPsl) ----------------------------------------
+ * For every chain c of the set, over all aligned positions of its blocks, the
+ * four exclusive classes aliStringToPsl counts
+ * (kent/src/hg/mouseStuff/chainToPsl/chainToPsl.c:106-131), tested in its
+ * order on text as twoBitReadSeqFragExt(doMask=TRUE) gives it:
+ *   counts[c*4 + 3] nCount    either base is N (in any case)
+ *   counts[c*4 + 0] match     else equal bases, the TARGET base upper case
+ *   counts[c*4 + 2] repMatch  else equal bases, the target base lower case
+ *   counts[c*4 + 1] misMatch  else (whatever the case)
+ * -- the order of the PSL columns.  The query's case is never read.  A '-'
+ * query is the reverse complement of the whole resident sequence, as there
+ * (:55-56, with the sequence's own size, not the chain header's qSize): block
+ * query coordinates are the chain's, unshifted.  Exact integers.  The target
+ * side needs the soft-mask plane (GAC_E_STATE), the query side does not; a
+ * NULL or orphaned set is GAC_E_ARG; an empty set writes nothing.  No scoring
+ * setup is needed.  Host buffer [n_chains][4], synchronous. */
+int gac_chain_psl_counts(gac_ctx *ctx, const gac_chainset *cs, int64_t *counts);
+/* The same counts (chainToPsl.c:106-131) into a device buffer on `stream`
+ * (NULL: the context's); returns once enqueued. */
+int gac_chain_psl_counts_device(gac_ctx *ctx, const gac_chainset *cs, int64_t *d_counts,
+                                void *stream);
 
 /* ---- alignment text (chainToAxt) ------------------------------------------
  * A piece is a window of consecutive blocks of one chain (gac_window: chain,
