@@ -192,6 +192,7 @@ struct gac_net {
     int64_t n_top[2];
     int32_t *nlen[2]; /* [GAC_T] / [GAC_Q]: the sequence names' lengths */
     int sides; /* bit 1 << side: side netted */
+    int lookahead; /* GAC_NET_LOOKAHEAD (default on): pipelined chain loops */
     atomic_int free_next; /* gac_net_free's worker cursor */
 };
 
@@ -812,6 +813,19 @@ static int is_haplotype(const char *name) {
     return strstr(name, "_hap") != NULL || strstr(name, "_alt") != NULL;
 }
 
+/* One chain on one side, as the netting loops need it: the per-side lists
+ * hold these records in list order (input order within a sequence), so a
+ * loop streams them instead of gathering blk_off, the strand, the sequence
+ * size and the span from six arrays at a scattered chain id. */
+typedef struct crec {
+    int64_t boff;   /* blk_off[chain] */
+    int32_t chain;
+    int32_t nb;     /* block count */
+    int32_t s, e;   /* the chain's span on this side, + strand coordinates */
+    int32_t qsize;  /* size of its query sequence */
+    int32_t minus;  /* query strand is '-' */
+} crec;
+
 /* Blocks of a chain that can touch spaces inside [A, B) (the whole chain
  * when A/B are INT32_MIN/MAX): those ending after A and starting before B,
  * plus one neighbour on each side, as an index range [*lo, *hi) over the
@@ -838,14 +852,14 @@ static int is_haplotype(const char *name) {
     } while (0)
 
 /* addChainQ (chainNet.c:610-679) */
-static void add_chain_q(const gac_net *net, nwork *n, int64_t c, nchrom *qc, int A, int B) {
+static void add_chain_q(const gac_net *net, nwork *n, const crec *r, nchrom *qc, int A, int B) {
     const gac_net_input *in = &net->in;
-    const int64_t b0 = in->blk_off[c];
-    const int nb = (int)(in->blk_off[c + 1] - b0);
+    const int64_t b0 = r->boff;
+    const int nb = r->nb;
     const int32_t *bt = in->blk_t + b0, *bq = in->blk_q + b0, *bs = in->blk_size + b0;
-    const int minus = in->q_strand[c] != 0;
-    const int qsize = in->q_sizes[in->q_seq[c]];
-    int qs = in->q_start[c], qe = in->q_end[c];
+    const int minus = r->minus;
+    const int qsize = r->qsize;
+    const int qs = r->s, qe = r->e; /* (+ strand coordinates already) */
     int l0 = 0, l1 = nb, *lo = &l0, *hi = &l1;
     if (A != INT32_MIN || B != INT32_MAX) {
         if (!minus) {
@@ -871,9 +885,6 @@ static void add_chain_q(const gac_net *net, nwork *n, int64_t c, nchrom *qc, int
             }
         }
     } else {
-        int t = qs;
-        qs = qsize - qe;
-        qe = qsize - t;
         for (int i = l0; i < l1; ++i) {
             int j = nb - 1 - i; /* original index */
             n->rs[i - l0] = qsize - (bq[j] + bs[j]);
@@ -885,18 +896,18 @@ static void add_chain_q(const gac_net *net, nwork *n, int64_t c, nchrom *qc, int
             }
         }
     }
-    add_chain_side(net, n, qc, (int32_t)c, m, n->rs, n->re, n->ros, n->roe, n->ro, minus, -1, qs,
+    add_chain_side(net, n, qc, r->chain, m, n->rs, n->re, n->ros, n->roe, n->ro, minus, -1, qs,
                    qe, -1);
 }
 
 /* addChainT (chainNet.c:557-608) */
-static void add_chain_t(const gac_net *net, nwork *n, int64_t c, nchrom *tc, int A, int B) {
+static void add_chain_t(const gac_net *net, nwork *n, const crec *r, nchrom *tc, int A, int B) {
     const gac_net_input *in = &net->in;
-    const int64_t b0 = in->blk_off[c];
-    const int nb = (int)(in->blk_off[c + 1] - b0);
+    const int64_t b0 = r->boff;
+    const int nb = r->nb;
     const int32_t *bt = in->blk_t + b0, *bq = in->blk_q + b0, *bs = in->blk_size + b0;
-    const int minus = in->q_strand[c] != 0;
-    const int qsize = in->q_sizes[in->q_seq[c]];
+    const int minus = r->minus;
+    const int qsize = r->qsize;
     int l0 = 0, l1 = nb, *lo = &l0, *hi = &l1;
     if (A != INT32_MIN || B != INT32_MAX) {
 #define TST(i) bt[i]
@@ -920,8 +931,8 @@ static void add_chain_t(const gac_net *net, nwork *n, int64_t c, nchrom *tc, int
             n->roe[b - l0] = qe;
         }
     }
-    add_chain_side(net, n, tc, (int32_t)c, m, n->rs, n->re, n->ros, n->roe, n->ro, 0,
-                   minus ? qsize : -1, in->t_start[c], in->t_end[c], l0);
+    add_chain_side(net, n, tc, r->chain, m, n->rs, n->re, n->ros, n->roe, n->ro, 0,
+                   minus ? qsize : -1, r->s, r->e, l0);
 }
 
 /* ------------------------------------------------------------ finish */
@@ -1256,7 +1267,7 @@ static void *fin_thread(void *arg) {
 typedef struct net_task {
     int side;
     int32_t chrom;
-    const int64_t *chains;
+    const crec *recs; /* its chains in input order */
     int64_t n;
 } net_task;
 
@@ -1271,26 +1282,90 @@ static int net_task_cmp(const void *a, const void *b) {
 
 /* add chain c to side `side` of its sequence, whose space index is ch;
  * [A, B): the region ch covers (INT32_MIN/MAX: the whole sequence) */
-static void add_chain(const gac_net *net, nwork *w, int side, int64_t c, nchrom *ch, int A, int B) {
+static void add_chain(const gac_net *net, nwork *w, int side, const crec *r, nchrom *ch, int A,
+                      int B) {
     if (side == GAC_T)
-        add_chain_t(net, w, c, ch, A, B);
+        add_chain_t(net, w, r, ch, A, B);
     else
-        add_chain_q(net, w, c, ch, A, B);
+        add_chain_q(net, w, r, ch, A, B);
 }
 
-/* a chain's range on one side (+ strand coordinates) */
-static void chain_span(const gac_net *net, int side, int64_t c, int *s, int *e) {
-    const gac_net_input *in = &net->in;
-    if (side == GAC_T) {
-        *s = in->t_start[c];
-        *e = in->t_end[c];
-    } else if (in->q_strand[c]) {
-        const int qsize = in->q_sizes[in->q_seq[c]];
-        *s = qsize - in->q_end[c];
-        *e = qsize - in->q_start[c];
-    } else {
-        *s = in->q_start[c];
-        *e = in->q_end[c];
+/* ---- the chain loops, software-pipelined ----
+ * A chain's netting starts with dependent cache misses: its record, then the
+ * first lines of its slice of blk_t/blk_q/blk_size.  The chains of a list are
+ * scattered over the input, so nothing brings those lines in ahead of time;
+ * net_chains does, for the chains a few places further down the list, while
+ * the current chain is netted:
+ *   LA_REC ahead: the record's line (the list is a stream; this only runs
+ *                 ahead of the hardware's own prefetch at a list's start);
+ *   LA_BLK ahead: the block lines add_chain_t/q read first -- the head of the
+ *                 slice, the tail for a '-' chain on the query side (its
+ *                 blocks are walked backwards), and for a region [A, B) the
+ *                 first probes of SLICE's binary search.
+ * It reads nothing but the records (never past the list's end) and writes
+ * nothing.  Distances of 2 to 8 chains for the block lines measured the same
+ * on the MI355X host; a look-ahead descent of the space index
+ * for the chain two places on did not pay at 16 threads and was taken out.
+ * GAC_NET_LOOKAHEAD=0: the plain loops. */
+#define LA_REC 8
+#define LA_BLK 4
+
+/* read at every build (into gac_net.lookahead), so one process can A/B it */
+static int net_lookahead_env(void) {
+    const char *s = getenv("GAC_NET_LOOKAHEAD");
+    return !(s && s[0] == '0');
+}
+
+/* the lines of a chain's blocks that add_chain_t/q will read first */
+static inline void la_blocks(const gac_net_input *in, int side, const crec *r, int A, int B) {
+    const int nb = r->nb;
+    if (nb <= 0)
+        return;
+    const int back = side == GAC_Q && r->minus;
+    const int32_t *own = (side == GAC_T ? in->blk_t : in->blk_q) + r->boff;
+    const int32_t *oth = (side == GAC_T ? in->blk_q : in->blk_t) + r->boff;
+    const int32_t *sz = in->blk_size + r->boff;
+    if ((A != INT32_MIN || B != INT32_MAX) && nb > 16) {
+        /* SLICE: the middle block, then one of the quarter blocks (reversed
+         * list order on the query side of a '-' chain) */
+        const int m = nb >> 1, q1 = nb >> 2, q3 = (m + 1 + nb) >> 1;
+        const int p[3] = {back ? nb - 1 - m : m, back ? nb - 1 - q1 : q1,
+                          back ? nb - 1 - (q3 < nb ? q3 : nb - 1) : (q3 < nb ? q3 : nb - 1)};
+        for (int k = 0; k < 3; ++k) {
+            __builtin_prefetch(own + p[k]);
+            __builtin_prefetch(sz + p[k]);
+        }
+        return;
+    }
+    const int at = back ? nb - 1 : 0;
+    __builtin_prefetch(own + at);
+    __builtin_prefetch(oth + at);
+    __builtin_prefetch(sz + at);
+    if (nb > 16) { /* the next line in walking order */
+        const int at2 = back ? nb - 17 : 16;
+        __builtin_prefetch(own + at2);
+        __builtin_prefetch(oth + at2);
+        __builtin_prefetch(sz + at2);
+    }
+}
+
+/* net recs[0, n) in order into ch */
+static void net_chains(const gac_net *net, nwork *w, int side, const crec *recs, int64_t n,
+                       nchrom *ch, int A, int B) {
+    if (!net->lookahead) {
+        for (int64_t i = 0; i < n; ++i)
+            add_chain(net, w, side, &recs[i], ch, A, B);
+        return;
+    }
+    /* fill: the first chains' lines, as far as each stage looks */
+    for (int64_t i = 0; i < LA_BLK && i < n; ++i)
+        la_blocks(&net->in, side, &recs[i], A, B);
+    for (int64_t i = 0; i < n; ++i) {
+        if (i + LA_REC < n)
+            __builtin_prefetch(&recs[i + LA_REC]);
+        if (i + LA_BLK < n)
+            la_blocks(&net->in, side, &recs[i + LA_BLK], A, B);
+        add_chain(net, w, side, &recs[i], ch, A, B);
     }
 }
 
@@ -1315,7 +1390,7 @@ typedef struct region {
     nchrom ch;          /* its own space index (built by the worker that nets it) */
     const sitem *sp;    /* its spaces, in order */
     int64_t n_sp;
-    int64_t *chains;    /* remaining chains overlapping it, in order */
+    crec *chains;       /* remaining chains overlapping it, in order (records copied) */
     int64_t n_chains;
     int64_t work;
     int side;
@@ -1324,15 +1399,10 @@ typedef struct region {
 
 typedef struct big_net {
     net_task *t;
-    /* per chain of the task, in its order: span on this side and block
-     * count, gathered once (the chains of one side lie all over the input's
-     * arrays; the cut placement passes over them several times) */
-    int32_t *ss, *se;
-    int64_t *nbk;
     double t_start, t_gather, t_add, t_cut, t_reg; /* (GAC_TIMING laps of the prefix) */
     int64_t m;          /* chains netted sequentially first */
     sitem *spaces;      /* all spaces after the prefix */
-    int64_t *lists;     /* region chain lists, back to back */
+    crec *lists;        /* region chain lists, back to back */
     region *reg;
     int32_t n_reg;
 } big_net;
@@ -1444,8 +1514,8 @@ static int32_t place_cuts(const gac_net *net, const big_net *B, const sitem *sp,
     int64_t *bin = calloc(NB + 1, 8), *dif = calloc(NB + 1, 8), tot = 0;
     const double scale = (double)NB / (size > 0 ? size : 1);
     for (int64_t i = 0; i < rest; ++i) { /* (spread as a difference array) */
-        const int cs = B->ss[B->m + i], ce = B->se[B->m + i];
-        const int64_t w = 8 + B->nbk[B->m + i];
+        const int cs = t->recs[B->m + i].s, ce = t->recs[B->m + i].e;
+        const int64_t w = 8 + t->recs[B->m + i].nb;
         int b0 = (int)(cs * scale), b1 = (int)((ce > cs ? ce - 1 : cs) * scale);
         b0 = b0 < 0 ? 0 : (b0 >= NB ? NB - 1 : b0);
         b1 = b1 < b0 ? b0 : (b1 >= NB ? NB - 1 : b1);
@@ -1494,10 +1564,10 @@ static int32_t place_cuts(const gac_net *net, const big_net *B, const sitem *sp,
     /* region work */
     int64_t *rw = calloc((size_t)nc + 1, 8), mx = 0;
     for (int64_t i = 0; i < rest; ++i) {
-        const int cs = B->ss[B->m + i], ce = B->se[B->m + i];
+        const int cs = t->recs[B->m + i].s, ce = t->recs[B->m + i].e;
         const int64_t a = upper_bound32(cuts, nc, cs), b = upper_bound32(cuts, nc, ce > cs ? ce - 1 : cs);
         for (int64_t r = a; r <= b; ++r)
-            rw[r] += chain_work_in(cs, ce, B->nbk[B->m + i], r ? cuts[r - 1] : 0,
+            rw[r] += chain_work_in(cs, ce, t->recs[B->m + i].nb, r ? cuts[r - 1] : 0,
                                    r < nc ? cuts[r] : size);
     }
     for (int32_t r = 0; r <= nc; ++r)
@@ -1520,22 +1590,6 @@ static void big_prefix(gac_net *n, nwork *w, big_net *B, int nthreads) {
     const int32_t want = 4 * nthreads;
     int32_t *cuts = malloc((size_t)want * 4);
     B->t_start = mono_s();
-    B->ss = malloc((size_t)(t->n ? t->n : 1) * 4);
-    B->se = malloc((size_t)(t->n ? t->n : 1) * 4);
-    B->nbk = malloc((size_t)(t->n ? t->n : 1) * 8);
-    for (int64_t i = 0; i < t->n; ++i) {
-        const int64_t c = t->chains[i];
-        if (i + 8 < t->n) {
-            const int64_t d = t->chains[i + 8];
-            __builtin_prefetch(&n->in.blk_off[d]);
-            __builtin_prefetch(t->side == GAC_T ? &n->in.t_start[d] : &n->in.q_start[d]);
-        }
-        int cs, ce;
-        chain_span(n, t->side, c, &cs, &ce);
-        B->ss[i] = cs;
-        B->se[i] = ce;
-        B->nbk[i] = n->in.blk_off[c + 1] - n->in.blk_off[c];
-    }
     /* the prefix doubles from 8 chains until the regions balance: the
      * first chains leave one space over everything they did not reach */
     int64_t m = t->n < 8 ? t->n : 8, done = 0;
@@ -1546,8 +1600,8 @@ static void big_prefix(gac_net *n, nwork *w, big_net *B, int nthreads) {
     const double t_gather = t0 - B->t_start;
     for (;;) {
         double ta = mono_s();
-        for (; done < m; ++done)
-            add_chain(n, w, t->side, t->chains[done], c, INT32_MIN, INT32_MAX);
+        net_chains(n, w, t->side, t->recs + done, m - done, c, INT32_MIN, INT32_MAX);
+        done = m;
         double tb = mono_s();
         t_add += tb - ta;
         B->m = m;
@@ -1581,19 +1635,19 @@ static void big_prefix(gac_net *n, nwork *w, big_net *B, int nthreads) {
     int64_t *cnt = calloc((size_t)nreg + 1, 8);
     int32_t *ra = malloc((size_t)(rest ? rest : 1) * 4), *rb = malloc((size_t)(rest ? rest : 1) * 4);
     for (int64_t i = 0; i < rest; ++i) {
-        const int cs = B->ss[m + i], ce = B->se[m + i];
+        const int cs = t->recs[m + i].s, ce = t->recs[m + i].e;
         ra[i] = (int32_t)upper_bound32(cuts, nreg - 1, cs);
         rb[i] = (int32_t)upper_bound32(cuts, nreg - 1, ce > cs ? ce - 1 : cs);
         for (int32_t r = ra[i]; r <= rb[i]; ++r) {
             ++cnt[r];
-            B->reg[r].work += chain_work_in(cs, ce, B->nbk[m + i], r ? cuts[r - 1] : 0,
+            B->reg[r].work += chain_work_in(cs, ce, t->recs[m + i].nb, r ? cuts[r - 1] : 0,
                                             r < nreg - 1 ? cuts[r] : c->size);
         }
     }
     int64_t tot = 0;
     for (int32_t r = 0; r < nreg; ++r)
         tot += cnt[r];
-    B->lists = malloc((size_t)(tot ? tot : 1) * 8);
+    B->lists = malloc((size_t)(tot ? tot : 1) * sizeof(crec));
     tot = 0;
     for (int32_t r = 0; r < nreg; ++r) {
         B->reg[r].chains = B->lists + tot;
@@ -1601,7 +1655,7 @@ static void big_prefix(gac_net *n, nwork *w, big_net *B, int nthreads) {
     }
     for (int64_t i = 0; i < rest; ++i)
         for (int32_t r = ra[i]; r <= rb[i]; ++r)
-            B->reg[r].chains[B->reg[r].n_chains++] = t->chains[m + i];
+            B->reg[r].chains[B->reg[r].n_chains++] = t->recs[m + i];
     free(cnt);
     free(ra);
     free(rb);
@@ -1610,17 +1664,11 @@ static void big_prefix(gac_net *n, nwork *w, big_net *B, int nthreads) {
     B->t_add = t_add;
     B->t_cut = t_cut;
     B->t_reg = mono_s() - t0 - t_add - t_cut;
-    free(B->ss);
-    free(B->se);
-    free(B->nbk);
-    B->ss = B->se = NULL;
-    B->nbk = NULL;
 }
 
 static void net_region(gac_net *n, nwork *w, region *R) {
     sp_bulk(w, &R->ch, R->sp, R->n_sp);
-    for (int64_t i = 0; i < R->n_chains; ++i)
-        add_chain(n, w, R->side, R->chains[i], &R->ch, R->a, R->b);
+    net_chains(n, w, R->side, R->chains, R->n_chains, &R->ch, R->a, R->b);
 }
 
 typedef struct net_job {
@@ -1653,8 +1701,7 @@ static void net_small(gac_net *n, nwork *w, const net_task *t) {
     c->root = gap_new(w, 0, c->size, 0, 0);
     c->root->pidx = t->chrom;
     sp_init(w, c, 0, c->size, c->root);
-    for (int64_t i = 0; i < t->n; ++i)
-        add_chain(n, w, t->side, t->chains[i], c, INT32_MIN, INT32_MAX);
+    net_chains(n, w, t->side, t->recs, t->n, c, INT32_MIN, INT32_MAX);
 }
 
 static double mono_s(void) {
@@ -1735,6 +1782,127 @@ static void *chain_ali_thread(void *arg) {
     }
 }
 
+/* ---- the per-side chain lists, built on all threads ----
+ * A counting sort by sequence that keeps input order inside a sequence:
+ * every thread counts the chains of one contiguous range of the input per
+ * sequence, a prefix over (sequence, range) gives each range its place in
+ * every sequence's list, and the ranges then write their records there --
+ * range by range in input order, so the scatter is stable.  Chains of
+ * haplotype queries are left out of both sides (unless incl_hap). */
+typedef struct sl_job {
+    const gac_net_input *in;
+    const uint8_t *skip;
+    int64_t nn, per;
+    int nr, phase;
+    int64_t *th, *qh; /* [nr][nt], [nr][nq]: counts, then write cursors */
+    crec *tl, *ql;
+    _Atomic int next;
+} sl_job;
+
+static void *sl_thread(void *arg) {
+    sl_job *S = arg;
+    const gac_net_input *in = S->in;
+    for (;;) {
+        const int r = atomic_fetch_add(&S->next, 1);
+        if (r >= S->nr)
+            return NULL;
+        const int64_t a = r * S->per, b = a + S->per < S->nn ? a + S->per : S->nn;
+        int64_t *th = S->th + (size_t)r * (in->n_tseq > 0 ? in->n_tseq : 1);
+        int64_t *qh = S->qh + (size_t)r * (in->n_qseq > 0 ? in->n_qseq : 1);
+        for (int64_t c = a; c < b; ++c) {
+            const int32_t q = in->q_seq[c], t = in->t_seq[c];
+            if (S->skip[q])
+                continue;
+            if (S->phase == 0) {
+                ++th[t];
+                ++qh[q];
+                continue;
+            }
+            const int minus = in->q_strand[c] != 0;
+            const int32_t qsize = in->q_sizes[q];
+            crec R = {in->blk_off[c], (int32_t)c, (int32_t)(in->blk_off[c + 1] - in->blk_off[c]),
+                      in->t_start[c], in->t_end[c], qsize, minus};
+            S->tl[th[t]++] = R;
+            R.s = minus ? qsize - in->q_end[c] : in->q_start[c];
+            R.e = minus ? qsize - in->q_start[c] : in->q_end[c];
+            S->ql[qh[q]++] = R;
+        }
+    }
+}
+
+/* chains [0, nn): *toff / *qoff = [n_seq + 1] list offsets per sequence,
+ * *tl / *ql = the records, each sequence's in input order; nthreads ranges */
+static void side_lists(const gac_net_input *in, const gac_net_opts *opt, int64_t nn, int nthreads,
+                       int64_t **toff, int64_t **qoff, crec **tl, crec **ql) {
+    const int32_t nt = in->n_tseq, nq = in->n_qseq;
+    sl_job S;
+    memset(&S, 0, sizeof(S));
+    S.in = in;
+    S.nn = nn;
+    S.nr = nthreads < 1 ? 1 : nthreads;
+    if (S.nr > nn / 4096 + 1) /* (a range is worth a thread from a few thousand chains) */
+        S.nr = (int)(nn / 4096 + 1);
+    S.per = (nn + S.nr - 1) / S.nr;
+    uint8_t *skip = calloc((size_t)(nq > 0 ? nq : 1), 1); /* haplotype queries, by sequence */
+    for (int32_t k = 0; k < nq && !opt->incl_hap; ++k)
+        skip[k] = (uint8_t)is_haplotype(in->q_names[k]);
+    S.skip = skip;
+    S.th = calloc((size_t)S.nr * (nt > 0 ? nt : 1), 8);
+    S.qh = calloc((size_t)S.nr * (nq > 0 ? nq : 1), 8);
+    atomic_init(&S.next, 0);
+    gac_run_threads(S.nr, sl_thread, &S);
+    *toff = calloc((size_t)(nt > 0 ? nt : 0) + 1, 8);
+    *qoff = calloc((size_t)(nq > 0 ? nq : 0) + 1, 8);
+    for (int side = 0; side < 2; ++side) {
+        const int32_t ns = side == GAC_T ? nt : nq;
+        int64_t *h = side == GAC_T ? S.th : S.qh, *off = side == GAC_T ? *toff : *qoff, at = 0;
+        for (int32_t k = 0; k < ns; ++k) {
+            off[k] = at;
+            for (int r = 0; r < S.nr; ++r) { /* count -> the range's first place */
+                const int64_t cnt = h[(size_t)r * ns + k];
+                h[(size_t)r * ns + k] = at;
+                at += cnt;
+            }
+        }
+        off[ns > 0 ? ns : 0] = at;
+    }
+    const int64_t tot = (*toff)[nt > 0 ? nt : 0];
+    S.tl = *tl = malloc((size_t)(tot ? tot : 1) * sizeof(crec));
+    S.ql = *ql = malloc((size_t)(tot ? tot : 1) * sizeof(crec));
+    S.phase = 1;
+    atomic_init(&S.next, 0);
+    gac_run_threads(S.nr, sl_thread, &S);
+    free(S.th);
+    free(S.qh);
+    free(skip);
+}
+
+int gac_net_chain_lists(const gac_net_input *in, const gac_net_opts *opt, int side, int nthreads,
+                        int64_t *off, int32_t *chains) {
+    gac_clear_error();
+    if (!in || !opt || !off || !chains || (side != GAC_T && side != GAC_Q) || nthreads < 1)
+        return gac_fail(GAC_E_ARG, "gac_net_chain_lists: bad argument");
+    for (int64_t c = 0; c < in->n_chains; ++c)
+        if (in->t_seq[c] < 0 || in->t_seq[c] >= in->n_tseq || in->q_seq[c] < 0 ||
+            in->q_seq[c] >= in->n_qseq)
+            return gac_fail(GAC_E_ARG, "chain %lld: sequence index out of range", (long long)c);
+    int64_t *toff, *qoff;
+    crec *tl, *ql;
+    side_lists(in, opt, in->n_chains, nthreads, &toff, &qoff, &tl, &ql);
+    const int32_t ns = side == GAC_T ? in->n_tseq : in->n_qseq;
+    const int64_t *o = side == GAC_T ? toff : qoff;
+    const crec *l = side == GAC_T ? tl : ql;
+    for (int32_t k = 0; k <= (ns > 0 ? ns : 0); ++k)
+        off[k] = o[k];
+    for (int64_t i = 0; i < o[ns > 0 ? ns : 0]; ++i)
+        chains[i] = l[i].chain;
+    free(toff);
+    free(qoff);
+    free(tl);
+    free(ql);
+    return GAC_OK;
+}
+
 int gac_net_build(const gac_net_input *in, const gac_net_opts *opt, gac_net **out) {
     return gac_net_build_sides(in, opt, (1 << GAC_T) | (1 << GAC_Q), out);
 }
@@ -1777,6 +1945,8 @@ static int net_build(const gac_net_input *in, const gac_net_opts *opt, int sides
     }
     /* chains to net: in order until the first below minScore (must be
      * sorted), haplotype queries skipped unless incl_hap */
+    struct timespec t_set0, t_set1;
+    clock_gettime(CLOCK_MONOTONIC, &t_set0);
     double last = -1;
     int64_t i;
     for (i = 0; i < in->n_chains; ++i) {
@@ -1795,33 +1965,12 @@ static int net_build(const gac_net_input *in, const gac_net_opts *opt, int sides
         }
     }
     const int64_t nn = i;
-    /* per (side, chromosome): its chains in order (counting sort) */
+    /* per (side, chromosome): its chains' records in input order */
     int32_t nt = in->n_tseq, nq = in->n_qseq;
-    int64_t *toff = calloc((size_t)nt + 1, 8), *qoff = calloc((size_t)nq + 1, 8);
-    int64_t *tl = malloc((size_t)(nn ? nn : 1) * 8), *ql = malloc((size_t)(nn ? nn : 1) * 8);
-    int64_t *tfill = malloc((size_t)(nt ? nt : 1) * 8), *qfill = malloc((size_t)(nq ? nq : 1) * 8);
-    uint8_t *skip = calloc((size_t)(nq ? nq : 1), 1); /* haplotype queries, by sequence */
-    for (int32_t k = 0; k < nq && !opt->incl_hap; ++k)
-        skip[k] = (uint8_t)is_haplotype(in->q_names[k]);
-    for (int64_t c = 0; c < nn; ++c) {
-        if (skip[in->q_seq[c]])
-            continue;
-        ++toff[in->t_seq[c] + 1];
-        ++qoff[in->q_seq[c] + 1];
-    }
-    for (int32_t k = 0; k < nt; ++k)
-        toff[k + 1] += toff[k];
-    for (int32_t k = 0; k < nq; ++k)
-        qoff[k + 1] += qoff[k];
-    memcpy(tfill, toff, (size_t)nt * 8);
-    memcpy(qfill, qoff, (size_t)nq * 8);
-    for (int64_t c = 0; c < nn; ++c) {
-        if (skip[in->q_seq[c]])
-            continue;
-        tl[tfill[in->t_seq[c]]++] = c;
-        ql[qfill[in->q_seq[c]]++] = c;
-    }
-    free(skip);
+    int64_t *toff, *qoff;
+    crec *tl, *ql;
+    side_lists(in, opt, nn, n->n_w, &toff, &qoff, &tl, &ql);
+    n->lookahead = net_lookahead_env();
     for (int side = 0; side < 2; ++side) {
         int32_t cnt = side == GAC_T ? nt : nq;
         const char *const *names = side == GAC_T ? in->t_names : in->q_names;
@@ -1882,21 +2031,28 @@ static int net_build(const gac_net_input *in, const gac_net_opts *opt, int sides
     J2.rq = malloc((size_t)(J2.nrq ? J2.nrq : 1) * sizeof(region *));
     struct timespec t_add0, t_add1;
     clock_gettime(CLOCK_MONOTONIC, &t_add0);
+    t_set1 = t_add0;
     J2.t0 = mono_s();
     const int64_t units = nsmall + (J.nbig ? n->n_w : 0);
     gac_run_threads(n->n_w < units ? n->n_w : (units ? (int)units : 1), net_thread, &J2);
     clock_gettime(CLOCK_MONOTONIC, &t_add1);
     if (getenv("GAC_TIMING")) {
+        fprintf(stderr, "[gac_net_build] set-up %.3f s (checks, per-side chain records of %lld chains, tasks; look-ahead %s)\n",
+                (t_set1.tv_sec - t_set0.tv_sec) + 1e-9 * (t_set1.tv_nsec - t_set0.tv_nsec),
+                (long long)nn, n->lookahead ? "on" : "off");
         fprintf(stderr, "[gac_net_build] addChainT/Q %.3f s (%d threads, largest task %lld chains; sequential prefixes done after %.3f s)\n",
                 (t_add1.tv_sec - t_add0.tv_sec) + 1e-9 * (t_add1.tv_nsec - t_add0.tv_nsec),
                 n->n_w, J.ntask ? (long long)J.task[0].n : 0LL, J2.prefix_s);
         for (int32_t b = 0; b < J.nbig; ++b) {
-            int64_t mx = 0;
-            for (int32_t r = 0; r < J.big[b].n_reg; ++r)
+            int64_t mx = 0, fewest = INT64_MAX;
+            for (int32_t r = 0; r < J.big[b].n_reg; ++r) {
                 mx = J.big[b].reg[r].work > mx ? J.big[b].reg[r].work : mx;
-            fprintf(stderr, "[gac_net_build] side %d seq %d: %lld chains, %lld sequential, %d regions (largest work %lld); prefix: gather %.3f, chains %.3f, cuts %.3f, regions %.3f s\n",
+                fewest = J.big[b].reg[r].n_chains < fewest ? J.big[b].reg[r].n_chains : fewest;
+            }
+            fprintf(stderr, "[gac_net_build] side %d seq %d: %lld chains, %lld sequential, %d regions (largest work %lld, shortest list %lld chains); prefix: gather %.3f, chains %.3f, cuts %.3f, regions %.3f s\n",
                     J.big[b].t->side, J.big[b].t->chrom, (long long)J.big[b].t->n,
-                    (long long)J.big[b].m, J.big[b].n_reg, (long long)mx, J.big[b].t_gather,
+                    (long long)J.big[b].m, J.big[b].n_reg, (long long)mx,
+                    (long long)(J.big[b].n_reg ? fewest : 0), J.big[b].t_gather,
                     J.big[b].t_add, J.big[b].t_cut, J.big[b].t_reg);
         }
     }
@@ -1913,8 +2069,6 @@ static int net_build(const gac_net_input *in, const gac_net_opts *opt, int sides
     free(qoff);
     free(tl);
     free(ql);
-    free(tfill);
-    free(qfill);
     n->n_netted = i;
     struct timespec t_fin0, t_fin1;
     clock_gettime(CLOCK_MONOTONIC, &t_fin0);

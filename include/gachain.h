@@ -675,6 +675,13 @@ int gac_net_build_sides(const gac_net_input *in, const gac_net_opts *opts, int s
  * the unselected ones are written as if they held no chains). */
 int gac_net_build_subset(const gac_net_input *in, const gac_net_opts *opts, const uint8_t *t_keep,
                          const uint8_t *q_keep, gac_net **out);
+/* Diagnostic: the per-sequence chain lists of one side as gac_net_build
+ * makes them on `nthreads` threads -- every chain of the input (no score
+ * cut), haplotype queries left out unless incl_hap; off[n_seq + 1] = each
+ * sequence's place in chains[], whose entries keep input order inside a
+ * sequence.  chains[] holds up to n_chains entries. */
+int gac_net_chain_lists(const gac_net_input *in, const gac_net_opts *opts, int side, int nthreads,
+                        int64_t *off, int32_t *chains);
 void gac_net_free(gac_net *net);
 /* number of input chains consumed (netted or skipped) before stopping */
 int64_t gac_net_netted(const gac_net *net);
