@@ -937,6 +937,8 @@ typedef struct po_job {
     _Atomic int64_t next;
     _Atomic int64_t done; /* runs formatted (GAC_TIMING: a mark when all are) */
     _Atomic int oom;
+    void (*on_formatted)(void *); /* called once, by the worker that ends the last run */
+    void *harg;
 } po_job;
 
 static void *po_thread(void *p) {
@@ -951,8 +953,12 @@ static void *po_thread(void *p) {
             J->buf[r] = o.p;
             J->len[r] = o.n;
             atomic_store_explicit(&J->ready[r], 1, memory_order_release);
-            if (atomic_fetch_add(&J->done, 1) + 1 == J->nr)
+            if (atomic_fetch_add(&J->done, 1) + 1 == J->nr) {
+                /* (acq_rel on done: every other run's fn_buf has returned) */
                 gac_mark("output: every run formatted");
+                if (J->on_formatted)
+                    J->on_formatted(J->harg);
+            }
             continue;
         }
         FILE *f = open_memstream(&J->buf[r], &J->len[r]);
@@ -976,6 +982,8 @@ static int par_format(int64_t nr, void (*fn)(FILE *f, int64_t r, void *arg),
     J.fn = fn;
     J.fn_buf = fn_buf;
     J.arg = arg;
+    J.on_formatted = NULL;
+    J.harg = NULL;
     J.buf = calloc((size_t)(nr > 0 ? nr : 1), sizeof(char *));
     J.len = calloc((size_t)(nr > 0 ? nr : 1), sizeof(size_t));
     J.ready = calloc((size_t)(nr > 0 ? nr : 1), sizeof(_Atomic int));
@@ -1230,14 +1238,20 @@ static int out_writers(void) {
 }
 
 static int par_output(FILE *out, int64_t nr, void (*fn)(FILE *f, int64_t r, void *arg),
-                      void (*fn_buf)(gac_obuf *o, int64_t r, void *arg), void *arg) {
-    if (nr <= 0)
+                      void (*fn_buf)(gac_obuf *o, int64_t r, void *arg), void *arg,
+                      void (*on_formatted)(void *), void *harg) {
+    if (nr <= 0) {
+        if (on_formatted) /* nothing to format: formatted already */
+            on_formatted(harg);
         return 0;
+    }
     po_job J;
     J.nr = nr;
     J.fn = fn;
     J.fn_buf = fn_buf;
     J.arg = arg;
+    J.on_formatted = on_formatted;
+    J.harg = harg;
     J.buf = calloc((size_t)nr, sizeof(char *));
     J.len = calloc((size_t)nr, sizeof(size_t));
     J.ready = calloc((size_t)nr, sizeof(_Atomic int));
@@ -1383,10 +1397,15 @@ static int par_output(FILE *out, int64_t nr, void (*fn)(FILE *f, int64_t r, void
 }
 
 int gac_par_output(FILE *out, int64_t nr, void (*fn)(FILE *f, int64_t r, void *arg), void *arg) {
-    return par_output(out, nr, fn, NULL, arg);
+    return par_output(out, nr, fn, NULL, arg, NULL, NULL);
 }
 
 int gac_par_output_buf(FILE *out, int64_t nr, void (*fn)(gac_obuf *o, int64_t r, void *arg),
                        void *arg) {
-    return par_output(out, nr, NULL, fn, arg);
+    return par_output(out, nr, NULL, fn, arg, NULL, NULL);
+}
+
+int gac_par_output_buf_ex(FILE *out, int64_t nr, void (*fn)(gac_obuf *o, int64_t r, void *arg),
+                          void *arg, void (*on_formatted)(void *), void *harg) {
+    return par_output(out, nr, NULL, fn, arg, on_formatted, harg);
 }

@@ -130,6 +130,12 @@ char *gac_obuf_reserve(gac_obuf *o, size_t k);
 void gac_obuf_printf(gac_obuf *o, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 int gac_par_output_buf(FILE *out, int64_t nr, void (*fn)(gac_obuf *o, int64_t r, void *arg),
                        void *arg);
+/* The same with a "formatted" signal: on_formatted(harg) is called once, by
+ * the worker that finishes the last run (every fn call has returned; the
+ * writer may still hold run buffers for a while), or by the caller when
+ * nr <= 0.  What fn reads may be released from then on. */
+int gac_par_output_buf_ex(FILE *out, int64_t nr, void (*fn)(gac_obuf *o, int64_t r, void *arg),
+                          void *arg, void (*on_formatted)(void *), void *harg);
 int gac_par_format_buf(int64_t nr, void (*fn)(gac_obuf *o, int64_t r, void *arg), void *arg,
                        char ***bufs, size_t **lens);
 /* the same runs formatted on worker threads and returned, not written */

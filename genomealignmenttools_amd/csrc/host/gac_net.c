@@ -1039,32 +1039,120 @@ static void *free_worker(void *arg) {
     }
 }
 
-void gac_net_free(gac_net *n) {
+/* The bulk of a net -- the workers' arenas and pools, the pre-order arrays
+ * and the per-chain counts -- released while the rest (the handle, the
+ * chromosome tables) stays for gac_net_free.  chainNet calls it from the
+ * writers' "formatted" signal: nothing reads a net's records once the last
+ * run of its text is formatted, and about 14 of 16 cores idle while the two
+ * writers copy the text out.  No side counts as netted afterwards (a later
+ * read fails with GAC_E_STATE); every freed pointer is cleared, so
+ * gac_net_free frees only what is left.
+ *
+ * pages_only: the pages are dropped (madvise, under the mm's read lock) and
+ * the mappings and heap blocks stay for gac_net_free, which then unmaps empty
+ * ranges.  munmap and free() of a large block take the mm's write lock, and
+ * a writer's own free() of a run buffer waits behind it. */
+typedef struct drop_regions {
+    char **p;
+    size_t *len;
+    size_t n, cap;
+    _Atomic size_t next;
+} drop_regions;
+
+static void drop_add(drop_regions *D, void *p, size_t len) {
+    if (!p || !len)
+        return;
+    /* (pieces of one arena block at most: the threads share a large array) */
+    for (size_t o = 0; o < len; o += ARENA_BLOCK) {
+        if (D->n == D->cap) {
+            D->cap = D->cap ? 2 * D->cap : 256;
+            D->p = realloc(D->p, D->cap * sizeof(char *));
+            D->len = realloc(D->len, D->cap * sizeof(size_t));
+        }
+        D->p[D->n] = (char *)p + o;
+        D->len[D->n++] = len - o < ARENA_BLOCK ? len - o : ARENA_BLOCK;
+    }
+}
+
+static void *drop_worker(void *arg) {
+    drop_regions *D = arg;
+    const uintptr_t pg = 4096;
+    for (;;) {
+        const size_t k = atomic_fetch_add(&D->next, 1);
+        if (k >= D->n)
+            return NULL;
+        const uintptr_t a = ((uintptr_t)D->p[k] + pg - 1) & ~(pg - 1);
+        const uintptr_t b = ((uintptr_t)D->p[k] + D->len[k]) & ~(pg - 1);
+        if (b > a)
+            madvise((void *)a, b - a, MADV_DONTNEED);
+    }
+}
+
+void gac_net_release(gac_net *n, int pages_only) {
     if (!n)
         return;
+    n->sides = 0;
+    /* (pages_only runs beside the net writers: on half the threads the pages
+     * are gone well inside the writers' tail -- 0.03 s of about 0.1 s at C5 --
+     * and the writers' copy into the page cache keeps its pace; on 16 the
+     * write stage grew by about half of what the free stage lost,
+     * profiles/r08rel) */
+    const char *ft = getenv("GAC_FREE_THREADS");
+    const int half = gac_host_threads() / 2 > 0 ? gac_host_threads() / 2 : 1;
+    const int t = ft && atoi(ft) > 0 ? atoi(ft) : (pages_only ? half : 16);
+    if (pages_only) {
+        drop_regions D;
+        memset(&D, 0, sizeof(D));
+        for (int i = 0; i < n->n_w; ++i)
+            for (size_t k = 0; k < n->w[i].ar.n; ++k)
+                drop_add(&D, n->w[i].ar.blocks[k], n->w[i].ar.sizes[k]);
+        for (int s = 0; s < 2; ++s) {
+            drop_add(&D, n->order[s], (size_t)n->n_order[s] * sizeof(nfill *));
+            drop_add(&D, n->pord[s], (size_t)n->n_order[s] * sizeof(int64_t));
+            drop_add(&D, n->top[s], (size_t)n->n_top[s] * sizeof(int64_t));
+        }
+        drop_add(&D, n->chain_ali, (size_t)n->in.n_chains * sizeof(int64_t));
+        atomic_init(&D.next, 0);
+        if (D.n)
+            gac_run_threads(D.n < (size_t)t ? (int)D.n : t, drop_worker, &D);
+        free(D.p);
+        free(D.len);
+        return;
+    }
     if (n->w) {
         if (g_free_madv < 0) {
             const char *e = getenv("GAC_FREE_MADV");
             g_free_madv = !(e && *e == '0');
         }
-        const char *ft = getenv("GAC_FREE_THREADS");
-        const int t = ft && atoi(ft) > 0 ? atoi(ft) : 16;
         atomic_store(&n->free_next, 0);
         gac_run_threads(n->n_w < t ? n->n_w : t, free_worker, n);
     }
     free(n->w);
+    n->w = NULL;
+    n->n_w = 0;
+    for (int s = 0; s < 2; ++s) {
+        free(n->order[s]);
+        free(n->pord[s]);
+        free(n->top[s]);
+        n->order[s] = NULL;
+        n->pord[s] = NULL;
+        n->top[s] = NULL;
+        n->n_order[s] = n->n_top[s] = 0;
+        __atomic_store_n(&n->pord_ok[s], 0, __ATOMIC_RELEASE);
+    }
+    free(n->chain_ali);
+    n->chain_ali = NULL;
+}
+
+void gac_net_free(gac_net *n) {
+    if (!n)
+        return;
+    gac_net_release(n, 0);
     free(n->chroms[0]);
     free(n->chroms[1]);
-    free(n->order[0]);
-    free(n->order[1]);
-    free(n->pord[0]);
-    free(n->pord[1]);
     pthread_mutex_destroy(&n->pord_mu);
-    free(n->top[0]);
-    free(n->top[1]);
     free(n->nlen[0]);
     free(n->nlen[1]);
-    free(n->chain_ali);
     free(n);
 }
 
@@ -2857,7 +2945,8 @@ static void *wmore_thread(void *arg) {
 }
 
 static int net_write_f(const gac_net *n, int side, const int64_t *tscores, FILE *f,
-                       const char *const *meta, int32_t n_meta);
+                       const char *const *meta, int32_t n_meta, void (*on_formatted)(void *),
+                       void *harg);
 
 /* "reached" flags: a fill prints when it passes and every ancestor fill
  * prints; parents precede children in pre-order, so runs that start at
@@ -2968,6 +3057,16 @@ static void *wreached_thread(void *arg) {
 
 int gac_net_write(const gac_net *n, int side, const int64_t *tscores, const char *path,
                   const char *const *meta, int32_t n_meta) {
+    return gac_net_write_ex(n, side, tscores, path, meta, n_meta, NULL, NULL);
+}
+
+/* Nothing below reads the net, the scores or the '#' lines once the hook has
+ * run: the '#' lines are in the stream's buffer before the first run, the
+ * flag arrays and the run buffers are the writer's own heap memory, and the
+ * close works on the descriptor alone. */
+int gac_net_write_ex(const gac_net *n, int side, const int64_t *tscores, const char *path,
+                     const char *const *meta, int32_t n_meta, void (*on_formatted)(void *),
+                     void *harg) {
     if (!n || !path || (side != GAC_T && side != GAC_Q))
         return gac_fail(GAC_E_ARG, "gac_net_write: bad argument");
     if (!(n->sides & (1 << side)))
@@ -2982,7 +3081,7 @@ int gac_net_write(const gac_net *n, int side, const int64_t *tscores, const char
         if (!f)
             return gac_fail(GAC_E_IO, "Can't open %s to write", path);
     }
-    int bad = net_write_f(n, side, tscores, f, meta, n_meta) != GAC_OK;
+    int bad = net_write_f(n, side, tscores, f, meta, n_meta, on_formatted, harg) != GAC_OK;
     if (close_it) {
         if (gac_close_output(f) != 0)
             bad = 1;
@@ -3001,7 +3100,7 @@ int gac_net_write_file(const gac_net *n, int side, const int64_t *tscores, FILE 
         return gac_fail(GAC_E_ARG, "gac_net_write_file: bad argument");
     if (!(n->sides & (1 << side)))
         return gac_fail(GAC_E_STATE, "gac_net_write_file: side %d was not netted", side);
-    if (net_write_f(n, side, tscores, f, meta, n_meta) != GAC_OK || fflush(f) != 0)
+    if (net_write_f(n, side, tscores, f, meta, n_meta, NULL, NULL) != GAC_OK || fflush(f) != 0)
         return gac_fail(GAC_E_IO, "write error");
     return GAC_OK;
 }
@@ -3062,7 +3161,8 @@ static void wjob_free_flags(wjob *J) {
 }
 
 static int net_write_f(const gac_net *n, int side, const int64_t *tscores, FILE *f,
-                       const char *const *meta, int32_t n_meta) {
+                       const char *const *meta, int32_t n_meta, void (*on_formatted)(void *),
+                       void *harg) {
     for (int32_t i = 0; i < n_meta; ++i)
         fprintf(f, "%s\n", meta[i]);
     wjob J;
@@ -3070,7 +3170,8 @@ static int net_write_f(const gac_net *n, int side, const int64_t *tscores, FILE 
     wjob_flags(&J, n, side, tscores);
     gac_mark(side ? "net_write q: format+write" : "net_write t: format+write");
     const int64_t nr = (J.nf + J.per - 1) / J.per;
-    int wbad = gac_par_output_buf(f, nr, write_run, &J);
+    /* (from the hook on, n, tscores and meta may be gone: see gac_net_write_ex) */
+    int wbad = gac_par_output_buf_ex(f, nr, write_run, &J, on_formatted, harg);
     wjob_free_flags(&J);
     gac_mark(side ? "net_write q: done" : "net_write t: done");
     return (ferror(f) || wbad) ? GAC_E_IO : GAC_OK;

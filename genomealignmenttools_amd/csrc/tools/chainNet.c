@@ -76,7 +76,60 @@ typedef struct net_out {
     gac_net_wpre *pre;
     pthread_t pre_th;
     int pre_started, pre_rc;
+    /* the "formatted" signal of a plain gac_net_write_ex (NULL: none) */
+    void (*on_formatted)(void *);
+    void *harg;
 } net_out;
+
+/* The nets and the chains released under the writers.  A net's text is
+ * formatted 0.12-0.13 s after its write starts (C5); its writer then copies
+ * the text into the page cache for 0.14-0.22 s more, reading only its own run
+ * buffers, while the other cores idle.  So each write signals "formatted"
+ * (gac_net_write_ex), and the signal that brings `pending` to zero starts one
+ * helper thread that does what the end of main did after both writes: the
+ * net's arenas and pre-order arrays (gac_net_release, GAC_FREE_THREADS wide),
+ * the chains' pages, the late frees.  main joins it where it used to free.
+ * The helper only drops the net's pages (madvise: the mm's read lock); the
+ * empty ranges are unmapped by main's gac_net_free in about 10 ms.  Unmapping
+ * them under the writers too (GAC_EARLY_FREE=2) measured slower: munmap takes
+ * the mm's write lock, and the writers' free() of run buffers waits behind it
+ * (C5 step medians 1347-1354 vs 1381-1407 ms, parent 1405; profiles/r08rel).
+ * Off with GAC_EARLY_FREE=0, -nranks and GAC_NET_PREFORMAT=1 (their writes
+ * do not signal): then main frees everything after the writes, as before. */
+typedef struct net_release {
+    gac_net *net;
+    gt_chains *c;
+    atomic_int pending; /* net writes that have not signalled yet */
+    pthread_t th;
+    int unmap;   /* GAC_EARLY_FREE=2: unmap under the writers too, not only drop the pages */
+    int started; /* th runs (set by the last signal, read by main after both writes) */
+    int done;    /* the helper released everything (read after joining it) */
+} net_release;
+
+static void *release_thread(void *arg) {
+    net_release *R = arg;
+    gac_mark("release: start");
+    gac_net_release(R->net, !R->unmap);
+    gac_mark("release: net released");
+    gt_chains_drop_pages(R->c);
+    gt_free_late_all();
+    R->done = 1;
+    gac_mark("release: done");
+    return NULL;
+}
+
+/* (on an output worker thread; both nets' texts are complete when the count
+ * reaches zero -- the decrements order the other side's formatting before the
+ * helper's start) */
+static void net_formatted(void *arg) {
+    net_release *R = arg;
+    if (atomic_fetch_sub(&R->pending, 1) != 1)
+        return;
+    if (pthread_create(&R->th, NULL, release_thread, R) != 0)
+        return; /* (main releases after the writes) */
+    gt_helper_add(R->th); /* gt_abort joins it before exiting */
+    R->started = 1;
+}
 
 static gt_ranks g_rk;
 
@@ -168,8 +221,9 @@ static void *write_net(void *arg) {
         free(buf);
         return NULL;
     }
-    w->rc = gac_net_write(w->net, w->side, w->tscores, w->path, (const char *const *)w->c->meta,
-                          w->c->n_meta);
+    w->rc = gac_net_write_ex(w->net, w->side, w->tscores, w->path,
+                             (const char *const *)w->c->meta, w->c->n_meta, w->on_formatted,
+                             w->harg);
     if (w->rc != GAC_OK) /* thread-local error text */
         snprintf(w->err, sizeof(w->err), "%s", gac_last_error());
     return NULL;
@@ -599,7 +653,16 @@ int main(int argc, char *argv[]) {
      * whole preformatted net to insert the scores cost more (1.16 s from the
      * flags to the written net vs ~0.5 s streaming, r03e) */
     const char *pf = getenv("GAC_NET_PREFORMAT");
-    if (rescore && pf && *pf == '1') {
+    const char *ef = getenv("GAC_EARLY_FREE");
+    const int preformat = rescore && pf && *pf == '1';
+    net_release rel = {net, &c, 0, 0, ef && *ef == '2', 0, 0};
+    atomic_init(&rel.pending, 2);
+    if (!multi && !preformat && !(ef && *ef == '0'))
+        for (int k = 0; k < 2; ++k) {
+            wo[k].on_formatted = net_formatted;
+            wo[k].harg = &rel;
+        }
+    if (preformat) {
         wo[0].pre_started = pthread_create(&wo[0].pre_th, NULL, pre_net, &wo[0]) == 0;
         if (wo[0].pre_started)
             gt_helper_add(wo[0].pre_th);
@@ -773,11 +836,16 @@ int main(int argc, char *argv[]) {
     gt_stage("device close (rest)");
     gac_gapcalc_free(gap);
     gt_ranks_done(&g_rk);
-    /* The net's pools are unmapped on 8 threads: left to process teardown
-     * they are freed on one core after the output is complete. */
+    /* The net's pools are unmapped on several threads: left to process
+     * teardown they are freed on one core after the output is complete.
+     * Usually the release helper has done it while the nets were written. */
+    if (rel.started)
+        gt_helper_join(rel.th);
     gac_net_free(net);
-    gt_chains_drop_pages(&c);
-    gt_free_late_all();
+    if (!rel.done) {
+        gt_chains_drop_pages(&c);
+        gt_free_late_all();
+    }
     gt_stage("free nets and chains");
     gt_exit_ok();
 }

@@ -491,32 +491,47 @@ static void device_wait_done(gt_device *d) {
     pthread_mutex_unlock(&d->mu);
 }
 
-/* registered helper threads (gt_helper_add); touched by the main thread only */
+/* registered helper threads (gt_helper_add); the table is under g_helpers_mu:
+ * a worker thread may register one (chainNet's release helper is started from
+ * an output worker) while the main thread joins another */
 #define GT_MAX_HELPERS 8
 static pthread_t g_helpers[GT_MAX_HELPERS];
 static int g_n_helpers;
+static pthread_mutex_t g_helpers_mu = PTHREAD_MUTEX_INITIALIZER;
 
 void gt_helper_add(pthread_t th) {
-    if (g_n_helpers == GT_MAX_HELPERS)
+    pthread_mutex_lock(&g_helpers_mu);
+    const int full = g_n_helpers == GT_MAX_HELPERS;
+    if (!full)
+        g_helpers[g_n_helpers++] = th;
+    pthread_mutex_unlock(&g_helpers_mu);
+    if (full)
         gt_abort("gt_helper_add: too many helper threads\n");
-    g_helpers[g_n_helpers++] = th;
 }
 
 void gt_helper_join(pthread_t th) {
+    pthread_mutex_lock(&g_helpers_mu);
     for (int i = 0; i < g_n_helpers; ++i)
         if (pthread_equal(g_helpers[i], th)) {
             g_helpers[i] = g_helpers[--g_n_helpers];
             break;
         }
+    pthread_mutex_unlock(&g_helpers_mu);
     pthread_join(th, NULL);
 }
 
 static void join_live_device(void) {
-    /* helpers first: they may be waiting for the device themselves */
-    for (int i = 0; i < g_n_helpers; ++i)
-        if (!pthread_equal(pthread_self(), g_helpers[i]))
-            pthread_join(g_helpers[i], NULL);
+    /* helpers first: they may be waiting for the device themselves (joined
+     * outside the lock: a helper may register another while it ends) */
+    pthread_t hs[GT_MAX_HELPERS];
+    pthread_mutex_lock(&g_helpers_mu);
+    const int nh = g_n_helpers;
+    memcpy(hs, g_helpers, sizeof(hs));
     g_n_helpers = 0;
+    pthread_mutex_unlock(&g_helpers_mu);
+    for (int i = 0; i < nh; ++i)
+        if (!pthread_equal(pthread_self(), hs[i]))
+            pthread_join(hs[i], NULL);
     gt_device *d = g_live_dev;
     if (d && d->closing && !pthread_equal(pthread_self(), (pthread_t)d->close_th)) {
         pthread_join((pthread_t)d->close_th, NULL);

@@ -58,8 +58,9 @@ extern "C" {
  * built against minor m runs with any library of minor >= m):
  * 1 = the alignment text entry points (gac_axt_*).
  * 2 = gac_axt_cut and the clip-aware gac_axt_*_clip entry points (netToAxt).
- * 3 = gac_chain_psl_counts[_device] (chainToPsl). */
-#define GAC_ABI_MINOR 3
+ * 3 = gac_chain_psl_counts[_device] (chainToPsl).
+ * 4 = gac_net_write_ex and gac_net_release (chainNet frees a net under its writers). */
+#define GAC_ABI_MINOR 4
 
 /* return codes */
 #define GAC_OK 0
@@ -711,6 +712,26 @@ int gac_net_rescore_windows(const gac_net *net, int side, gac_window **windows, 
  * (<= 0 prints as 1); NULL = reference's proportional approximation. */
 int gac_net_write(const gac_net *net, int side, const int64_t *t_scores, const char *path,
                   const char *const *meta, int32_t n_meta);
+/* The same, with a "formatted" signal: on_formatted(harg) (may be NULL) is
+ * called once, from a worker thread, when the last piece of the side's text
+ * is formatted (or from the caller when the side has no fill).  From then on
+ * the call reads neither net, t_scores nor meta -- it only copies the text it
+ * holds to the file and closes it -- so the caller may release them while the
+ * write completes (gac_net_release).  The hook does not run when the call
+ * fails before formatting starts (bad argument, the file does not open). */
+int gac_net_write_ex(const gac_net *net, int side, const int64_t *t_scores, const char *path,
+                     const char *const *meta, int32_t n_meta, void (*on_formatted)(void *),
+                     void *harg);
+/* Release the bulk of a net (the fill/gap records, the pre-order arrays)
+ * ahead of gac_net_free, on several threads (GAC_FREE_THREADS; default 16,
+ * with pages_only half the host threads).
+ * pages_only != 0: only the pages go (madvise, which does not hold up other
+ * threads' malloc/free the way unmapping does); gac_net_free unmaps the then
+ * empty ranges.  Only gac_net_free (or another gac_net_release) may follow;
+ * any other call on the net fails with GAC_E_STATE.  No gac_net_* call on
+ * this net may be reading it: with gac_net_write_ex, call it once every
+ * write in flight has signalled. */
+void gac_net_release(gac_net *net, int pages_only);
 /* The same text written to an open stream (e.g. an open_memstream buffer:
  * chainNet -nranks formats a rank's part in memory, then writes it in place). */
 int gac_net_write_file(const gac_net *net, int side, const int64_t *t_scores, FILE *f,
