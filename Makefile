@@ -114,10 +114,13 @@ clean:
 # TEST INFRASTRUCTURE: axtChain's host half (front end + kd-tree DP) on a CPU
 # stand-in of the device ABI, for profiling in GPU-less containers.  Not part
 # of `all`; never shipped (oracle/cpu_gac_stub.c).
+# (the stand-in has no render jobs and no soft-mask request: the tool library
+# without the file that calls them)
+CPU_TOOL_LIB_SRC := $(filter-out %/gac_seqtool_dev.c,$(TOOL_LIB_SRC))
 cpu-axtchain: oracle/_build/axtChain_cpu
 
 oracle/_build/axtChain_cpu: $(CSRC)/tools/axtChain.c $(CSRC)/host/gac_axtchain.c \
-		$(CSRC)/host/gac_host.c oracle/cpu_gac_stub.c $(TOOL_LIB_SRC)
+		$(CSRC)/host/gac_host.c oracle/cpu_gac_stub.c $(CPU_TOOL_LIB_SRC)
 	@mkdir -p oracle/_build
 	$(CC) -O2 -g -mpopcnt -std=gnu11 -Wall -ffp-contract=off -Iinclude -I$(CSRC) -I$(CSRC)/host -I$(CSRC)/tools/lib $^ \
 	    -o $@ -lz -lm -lpthread $(CPU_EXTRA)
@@ -127,7 +130,7 @@ oracle/_build/axtChain_cpu: $(CSRC)/tools/axtChain.c $(CSRC)/host/gac_axtchain.c
 cpu-chainnet: oracle/_build/chainNet_cpu
 
 oracle/_build/chainNet_cpu: $(CSRC)/tools/chainNet.c $(CSRC)/host/gac_net.c \
-		$(CSRC)/host/gac_host.c oracle/cpu_gac_stub.c $(TOOL_LIB_SRC)
+		$(CSRC)/host/gac_host.c oracle/cpu_gac_stub.c $(CPU_TOOL_LIB_SRC)
 	@mkdir -p oracle/_build
 	$(CC) -O2 -g -mpopcnt -std=gnu11 -Wall -ffp-contract=off -Iinclude -I$(CSRC) -I$(CSRC)/host -I$(CSRC)/tools/lib $^ \
 	    -o $@ -lz -lm -lpthread $(CPU_EXTRA)
@@ -150,7 +153,7 @@ variant: $(HOST_OBJ)
 cpu-chaincleaner: oracle/_build/chainCleaner_cpu
 
 oracle/_build/chainCleaner_cpu: $(CSRC)/tools/chainCleaner.c $(CSRC)/host/gac_net.c \
-		$(CSRC)/host/gac_host.c oracle/cpu_gac_stub.c $(TOOL_LIB_SRC)
+		$(CSRC)/host/gac_host.c oracle/cpu_gac_stub.c $(CPU_TOOL_LIB_SRC)
 	@mkdir -p oracle/_build
 	$(CC) -O2 -g -mpopcnt -std=gnu11 -Wall -ffp-contract=off -Iinclude -I$(CSRC) -I$(CSRC)/host -I$(CSRC)/tools/lib $^ \
 	    -o $@ -lz -lm -lpthread $(CPU_EXTRA)

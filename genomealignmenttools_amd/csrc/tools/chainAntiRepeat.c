@@ -14,9 +14,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "gac_tool.h"
+#include "gac_seqtool.h"
 #include "gachain.h"
-#include "host/gac_host.h"
 
 static const gt_spec k_opts[] = {
     {"minScore", GT_INT},
@@ -34,21 +33,23 @@ static void usage(void) {
         "   -noCheckScore=N - score that will pass without checks (speed tweak)\n");
 }
 
-/* the range check of twoBitReadSeqFragExt (kent/src/lib/twoBit.c:744-751) for
- * the fragment nibTwoCacheSeqPart asks for (nibTwo.c:74-77) */
-static void check_frag(const char *name, int64_t start, int64_t end, int32_t seq_size) {
-    if (end == 0)
-        end = seq_size;
-    if (end > seq_size)
-        gt_abort("twoBitReadSeqFrag in %s end (%d) >= seqSize (%d)", name, (int)end, seq_size);
-    if (end - start < 1 || start < 0)
-        gt_abort("twoBitReadSeqFrag in %s start (%d) >= end (%d)", name, (int)start, (int)end);
-}
-
-/* both genome sides with the soft-mask plane (on the device thread) */
-static int want_softmask(gac_ctx *ctx) {
-    const int rc = gac_genome_want_softmask(ctx, GAC_T);
-    return rc != GAC_OK ? rc : gac_genome_want_softmask(ctx, GAC_Q);
+/* the per-chain aborts, in the reference's order: the target is fetched
+ * first (:141-149) */
+static void check_chain(const gs_env *k, int64_t i, int32_t ts, int32_t qs) {
+    const gt_chains *c = k->c;
+    const char *tn = c->tnames.names[c->tname[i]], *qn = c->qnames.names[c->qname[i]];
+    if (ts < 0)
+        gt_abort("%s is not in %s", tn, k->t2bit);
+    gs_check_frag(tn, c->tstart[i], c->tend[i], gac_genome_seq_size(k->ctx, GAC_T, ts));
+    if (qs < 0)
+        gt_abort("%s is not in %s", qn, k->q2bit);
+    const int32_t S = gac_genome_seq_size(k->ctx, GAC_Q, qs);
+    /* a '-' query is fetched at [qSize - qEnd, qSize - qStart) with the
+     * header's qSize (:144-149) */
+    if (c->qstrand[i])
+        gs_check_frag(qn, (int64_t)c->qsize[i] - c->qend[i], (int64_t)c->qsize[i] - c->qstart[i], S);
+    else
+        gs_check_frag(qn, c->qstart[i], c->qend[i], S);
 }
 
 /* output items in input order: a '#' line (chain < 0: meta index in k) or a
@@ -80,18 +81,11 @@ int main(int argc, char *argv[]) {
     const int min_score = gt_opt_int("minScore", 5000);
     const int no_check = gt_opt_int("noCheckScore", 200000);
     const char *t2bit = argv[1], *q2bit = argv[2];
-    if (!gt_file_exists(t2bit))
-        gt_abort("ERROR: target 2bit file or nib directory %s does not exist\n", t2bit);
-    if (!gt_file_exists(q2bit))
-        gt_abort("ERROR: query 2bit file or nib directory %s does not exist\n", q2bit);
-    if (!gac_is_twobit_file(t2bit))
-        gt_abort("ERROR: only 2bit files are supported, not %s\n", t2bit);
-    if (!gac_is_twobit_file(q2bit))
-        gt_abort("ERROR: only 2bit files are supported, not %s\n", q2bit);
+    gs_check_twobits(t2bit, q2bit, "2bit file or nib directory");
 
     /* device open + genome upload (with the soft-mask plane) beside the parse */
     gt_device dev;
-    gt_device_on_open(want_softmask);
+    gt_device_on_open(gs_softmask_both);
     gt_stage("options + setup");
     gt_device_start(&dev, t2bit, q2bit, NULL, NULL);
 
@@ -107,58 +101,29 @@ int main(int argc, char *argv[]) {
     gt_stage("device open + 2bit genomes (rest)");
 
     /* the checked chains (:138, double against int), as a set of their own */
-    int64_t nc = 0, nb = 0;
+    uint8_t *keep = gs_alloc((size_t)c.n);
     for (int64_t i = 0; i < c.n; ++i)
-        if (c.score[i] < no_check) {
-            ++nc;
-            nb += c.blk_off[i + 1] - c.blk_off[i];
-        }
-    int64_t *sel = malloc((size_t)(nc ? nc : 1) * 8);
-    int32_t *tseq = malloc((size_t)(nc ? nc : 1) * 4), *qseq = malloc((size_t)(nc ? nc : 1) * 4);
-    uint8_t *strand = malloc((size_t)(nc ? nc : 1));
-    int64_t *boff = malloc((size_t)(nc + 1) * 8);
-    int32_t *bt = malloc((size_t)(nb ? nb : 1) * 4), *bq = malloc((size_t)(nb ? nb : 1) * 4);
-    int32_t *bs = malloc((size_t)(nb ? nb : 1) * 4);
+        keep[i] = c.score[i] < no_check;
     int32_t *tmap = gt_seq_map(ctx, GAC_T, &c.tnames), *qmap = gt_seq_map(ctx, GAC_Q, &c.qnames);
-    int64_t k = 0, b = 0;
-    boff[0] = 0;
-    for (int64_t i = 0; i < c.n; ++i) {
-        if (!(c.score[i] < no_check))
-            continue;
-        const char *tn = c.tnames.names[c.tname[i]], *qn = c.qnames.names[c.qname[i]];
-        const int32_t ts = tmap[c.tname[i]], qs = qmap[c.qname[i]];
-        if (ts < 0)
-            gt_abort("%s is not in %s", tn, t2bit);
-        check_frag(tn, c.tstart[i], c.tend[i], gac_genome_seq_size(ctx, GAC_T, ts));
-        if (qs < 0)
-            gt_abort("%s is not in %s", qn, q2bit);
-        const int32_t S = gac_genome_seq_size(ctx, GAC_Q, qs);
-        /* a '-' query is fetched at [qSize - qEnd, qSize - qStart) with the
-         * header's qSize (:144-149); the engine flips with the .2bit size S:
-         * the same bases lie at strand coordinates shifted by S - qSize */
-        int64_t shift = 0;
-        if (c.qstrand[i]) {
-            check_frag(qn, (int64_t)c.qsize[i] - c.qend[i], (int64_t)c.qsize[i] - c.qstart[i], S);
-            shift = (int64_t)S - c.qsize[i];
-        } else {
-            check_frag(qn, c.qstart[i], c.qend[i], S);
-        }
-        sel[k] = i;
-        tseq[k] = ts;
-        qseq[k] = qs;
-        strand[k] = c.qstrand[i];
-        for (int64_t j = c.blk_off[i]; j < c.blk_off[i + 1]; ++j, ++b) {
-            bt[b] = c.bt[j];
-            bq[b] = (int32_t)(c.bq[j] + shift);
-            bs[b] = c.bs[j];
-        }
-        boff[++k] = b;
-    }
+    const gs_env env = {&c, ctx, t2bit, q2bit};
+    gs_subset s;
+    gs_subset_build(&env, keep, c.tname, c.qname, tmap, qmap, check_chain, 0, &s);
     free(tmap);
     free(qmap);
-    gac_chainset_desc d = {nc, tseq, qseq, strand, boff, nb, bt, bq, bs};
+    free(keep);
+    /* the engine flips a '-' query with the .2bit size S, the reference with
+     * the header's qSize: the same bases lie at strand coordinates shifted by
+     * S - qSize */
+    for (int64_t k = 0; k < s.nc; ++k) {
+        const int64_t i = s.sel[k];
+        const int64_t shift = (int64_t)gac_genome_seq_size(ctx, GAC_Q, s.qseq[k]) - c.qsize[i];
+        if (c.qstrand[i] && shift)
+            for (int64_t b = s.boff[k]; b < s.boff[k + 1]; ++b)
+                s.bq[b] = (int32_t)(s.bq[b] + shift);
+    }
+    const int64_t nc = s.nc, *sel = s.sel;
     gac_chainset *cs = NULL;
-    gt_check(gac_chains_upload(ctx, &d, &cs));
+    gt_check(gac_chains_upload(ctx, &s.d, &cs));
     gt_stage("chains to HBM");
     int64_t *match = malloc((size_t)(nc ? nc : 1) * 4 * 8), *rep = malloc((size_t)(nc ? nc : 1) * 8);
     int64_t *total = malloc((size_t)(nc ? nc : 1) * 8);

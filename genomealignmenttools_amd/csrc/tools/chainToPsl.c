@@ -17,9 +17,8 @@
 #include <string.h>
 
 #include "gac_pslout.h"
-#include "gac_tool.h"
+#include "gac_seqtool.h"
 #include "gachain.h"
-#include "host/gac_host.h"
 
 static void usage(void) {
     gt_abort("chainToPsl - Convert chain file to psl format\n"
@@ -31,10 +30,6 @@ static void usage(void) {
              "The target and query lists can either be fasta files, nib files, 2bit files\n"
              "or a list of fasta, 2bit and/or nib files one per line\n");
 }
-
-/* the target side with the soft-mask plane (on the device thread); the
- * query's case is never read */
-static int want_softmask(gac_ctx *ctx) { return gac_genome_want_softmask(ctx, GAC_T); }
 
 typedef struct out_ctx {
     const gt_chains *c;
@@ -52,18 +47,12 @@ int main(int argc, char *argv[]) {
     if (argc != 7)
         usage();
     const char *t2bit = argv[4], *q2bit = argv[5];
-    if (!gt_file_exists(t2bit))
-        gt_abort("ERROR: target file %s does not exist\n", t2bit);
-    if (!gt_file_exists(q2bit))
-        gt_abort("ERROR: query file %s does not exist\n", q2bit);
-    if (!gac_is_twobit_file(t2bit))
-        gt_abort("ERROR: only 2bit files are supported, not %s\n", t2bit);
-    if (!gac_is_twobit_file(q2bit))
-        gt_abort("ERROR: only 2bit files are supported, not %s\n", q2bit);
+    gs_check_twobits(t2bit, q2bit, "file");
 
     /* device open + genome upload beside the parse */
     gt_device dev;
-    gt_device_on_open(want_softmask);
+    /* the target side with the soft-mask plane; the query's case is never read */
+    gt_device_on_open(gs_softmask_target);
     gt_stage("options + setup");
     gt_device_start(&dev, t2bit, q2bit, NULL, NULL);
     gt_verbose(1, "Scanning %s\n", t2bit);

@@ -144,7 +144,7 @@ void gt_stage(const char *what) {
     last_flt = ru.ru_minflt;
 }
 
-static double now_s(void) {
+double gt_now_s(void) {
     struct timespec ts;
     clock_gettime(CLOCK_MONOTONIC, &ts);
     return ts.tv_sec + 1e-9 * ts.tv_nsec;
@@ -174,7 +174,7 @@ void gt_device_on_open(int (*fn)(gac_ctx *)) { g_open_hook = fn; }
 
 static void *device_thread(void *arg) {
     gt_device *d = arg;
-    const double t0 = now_s();
+    const double t0 = gt_now_s();
     twobit_pre P;
     memset(&P, 0, sizeof(P));
     P.path[0] = d->t2bit;
@@ -184,7 +184,7 @@ static void *device_thread(void *arg) {
     if (!pre_ok)
         twobit_pre_thread(&P);
     int rc = gac_open(g_gpu, &d->ctx);
-    d->open_s = now_s() - t0;
+    d->open_s = gt_now_s() - t0;
     if (rc == GAC_OK && d->mat)
         rc = gac_set_scoring(d->ctx, d->mat, d->gap);
     if (rc == GAC_OK && g_open_hook) /* e.g. chainAntiRepeat asks for the soft-mask planes */
@@ -205,12 +205,12 @@ static void *device_thread(void *arg) {
         }
         const gt_runs *R = NULL;
         if (rc == GAC_OK && d->runs) { /* the word runs the chains need */
-            const double w0 = now_s();
+            const double w0 = gt_now_s();
             pthread_mutex_lock(&d->runs->mu);
             while (!d->runs->ready)
                 pthread_cond_wait(&d->runs->cv, &d->runs->mu);
             pthread_mutex_unlock(&d->runs->mu);
-            d->runs_wait_s += now_s() - w0;
+            d->runs_wait_s += gt_now_s() - w0;
             if (d->runs->ok < 0) { /* the tool is aborting: skip the upload */
                 gac_twobit_close(&P.tb[k]);
                 free(keep);
@@ -227,7 +227,7 @@ static void *device_thread(void *arg) {
             gac_twobit_close(&P.tb[k]);
         free(keep);
     }
-    d->load_s = now_s() - t0 - d->open_s;
+    d->load_s = gt_now_s() - t0 - d->open_s;
     if (rc != GAC_OK && !d->rc_err_set) /* the error text is thread-local */
         snprintf(d->err, sizeof(d->err), "%s", gac_last_error());
     pthread_mutex_lock(&d->mu);
@@ -381,7 +381,7 @@ static void bits_to_runs(const _Atomic uint64_t *bits, const int64_t *woff, int3
 }
 
 void gt_runs_build(gt_runs *R, const gt_chains *c, const char *t2bit, const char *q2bit) {
-    const double t0 = now_s();
+    const double t0 = gt_now_s();
     gac_twobit tb[2];
     int ok = gac_twobit_open_ex(t2bit, &tb[0], 0) == GAC_OK;
     if (ok && gac_twobit_open_ex(q2bit, &tb[1], 0) != GAC_OK) {
@@ -428,7 +428,7 @@ void gt_runs_build(gt_runs *R, const gt_chains *c, const char *t2bit, const char
         }
     }
     pthread_mutex_lock(&R->mu);
-    R->build_s = now_s() - t0;
+    R->build_s = gt_now_s() - t0;
     R->ok = ok;
     R->ready = 1;
     pthread_cond_broadcast(&R->cv);
@@ -823,13 +823,13 @@ typedef struct rank_wait {
 
 static void rank_wait_init(rank_wait *w, int r) {
     w->r = r;
-    w->t0 = now_s();
+    w->t0 = gt_now_s();
     w->next_check = 0;
     w->seen_alive = 0;
 }
 
 static void rank_wait_check(rank_wait *w, const gt_ranks *rk, const char *what) {
-    const double now = now_s();
+    const double now = gt_now_s();
     if (now < w->next_check)
         return;
     w->next_check = now + 0.05;
@@ -1956,7 +1956,7 @@ static int parse_chain(chunk *k) {
 
 static void *parse_chunk(void *arg) {
     chunk *k = arg;
-    k->t0 = now_s();
+    k->t0 = gt_now_s();
     k->c.blk_off = malloc(8);
     k->c.blk_off[0] = 0;
     if (k->lines > 0) { /* every block is a line: the arrays never grow */
@@ -1971,7 +1971,7 @@ static void *parse_chunk(void *arg) {
     if (r < 0)
         k->err_line = k->f.line;
     /* (f.line now counts the chunk's lines up to where it stopped) */
-    k->t1 = now_s();
+    k->t1 = gt_now_s();
     return NULL;
 }
 
@@ -2109,11 +2109,11 @@ static void read_chains(const char *path, gt_chains *c, double stop_below, int k
                         const gt_names *tkeep, const gt_names *qkeep) {
     memset(c, 0, sizeof(*c));
     const int timing = getenv("GAC_TIMING") != NULL;
-    double t_mark = now_s();
+    double t_mark = gt_now_s();
 #define RC_LAP(what)                                                               \
     do {                                                                           \
         if (timing) {                                                              \
-            const double t_ = now_s();                                             \
+            const double t_ = gt_now_s();                                             \
             fprintf(stderr, "[gt_read_chains] %-16s %.3f s\n", what, t_ - t_mark); \
             t_mark = t_;                                                           \
         }                                                                          \

@@ -16,9 +16,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "gac_tool.h"
+#include "gac_seqtool.h"
 #include "gachain.h"
-#include "host/gac_host.h"
 
 static const gt_spec k_opts[] = {
     {"scoreScheme", GT_STRING},
@@ -110,14 +109,7 @@ int main(int argc, char *argv[]) {
         gt_abort("-nranks needs an output file name (not stdout)");
     gt_set_gpu(gt_opt_int("gpu", multi ? rk.me : 0));
     const char *t2bit = argv[2], *q2bit = argv[3];
-    if (!gt_file_exists(t2bit))
-        gt_abort("ERROR: target 2bit file or nib directory %s does not exist\n", t2bit);
-    if (!gt_file_exists(q2bit))
-        gt_abort("ERROR: query 2bit file or nib directory %s does not exist\n", q2bit);
-    if (!gac_is_twobit_file(t2bit))
-        gt_abort("ERROR: only 2bit files are supported, not %s\n", t2bit);
-    if (!gac_is_twobit_file(q2bit))
-        gt_abort("ERROR: only 2bit files are supported, not %s\n", q2bit);
+    gs_check_twobits(t2bit, q2bit, "2bit file or nib directory");
 
     /* device open + genome upload run on a helper thread beside the parse */
     gt_device dev;
