@@ -229,6 +229,27 @@ static void *write_net(void *arg) {
     return NULL;
 }
 
+/* the rescored fills' scores to their fills (each fill is listed once) */
+typedef struct score_place {
+    int64_t *tscores;
+    const int64_t *rix, *g;
+    int64_t n;
+    _Atomic int64_t next;
+} score_place;
+
+static void *score_place_thread(void *arg) {
+    score_place *J = arg;
+    for (;;) {
+        const int64_t a = atomic_fetch_add(&J->next, 65536);
+        if (a >= J->n)
+            break;
+        const int64_t b = a + 65536 < J->n ? a + 65536 : J->n;
+        for (int64_t k = a; k < b; ++k)
+            J->tscores[J->rix[k]] = J->g[k];
+    }
+    return NULL;
+}
+
 /* block lists of the chains owning a rescored fill, copied in parallel */
 typedef struct subset_copy {
     const gt_chains *c;
@@ -720,8 +741,9 @@ int main(int argc, char *argv[]) {
             int32_t *ali = malloc(nr * 4);
             gt_check(gac_score_windows(ctx, pu.cs, r, nr, 0, g, NULL, ali));
             gt_stage("GPU fill rescoring");
-            for (int64_t k = 0; k < nr; ++k)
-                tscores[rix[k]] = g[k];
+            score_place sp = {tscores, rix, g, nr, 0};
+            atomic_init(&sp.next, 0);
+            gac_run_threads(gt_threads(), score_place_thread, &sp);
             gac_mark("scores placed");
             gt_free_late(g, (size_t)nr * 8);
             gt_free_late(ali, (size_t)nr * 4);
