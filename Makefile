@@ -21,9 +21,13 @@ CFLAGS   := -O2 -mpopcnt -std=gnu11 -fPIC -Wall -ffp-contract=off -Iinclude -I$(
 
 HOST_SRC := $(wildcard $(CSRC)/host/*.c)
 HOST_OBJ := $(patsubst $(CSRC)/host/%.c,$(OBJDIR)/host/%.o,$(HOST_SRC))
-HIP_SRC  := $(CSRC)/gac_kernels.hip $(CSRC)/gac_compose.hip $(CSRC)/gac_axtout.hip $(CSRC)/gac_dp.hip $(CSRC)/gac_dptree.hip $(CSRC)/gac_device.hip $(CSRC)/gac_comm.hip
+# kernels and their launchers, then the C ABI by subject (gac_device.hip:
+# scoring; gac_abi_*.hip; all over gac_ctx.h), then the rank communicator
+HIP_SRC  := $(CSRC)/gac_kernels.hip $(CSRC)/gac_compose.hip $(CSRC)/gac_axtout.hip $(CSRC)/gac_dp.hip $(CSRC)/gac_dptree.hip \
+            $(CSRC)/gac_abi_context.hip $(CSRC)/gac_abi_genome.hip $(CSRC)/gac_abi_chains.hip $(CSRC)/gac_device.hip \
+            $(CSRC)/gac_abi_dp.hip $(CSRC)/gac_abi_seqout.hip $(CSRC)/gac_comm.hip
 HIP_OBJ  := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
-HDRS     := include/gachain.h $(CSRC)/gac_kernels.h $(CSRC)/gac_dp.h $(wildcard $(CSRC)/host/*.h)
+HDRS     := include/gachain.h $(CSRC)/gac_kernels.h $(CSRC)/gac_dp.h $(CSRC)/gac_ctx.h $(wildcard $(CSRC)/host/*.h)
 
 EXECDIR  := $(PKG)/libexec
 # GPU tools: the binary lives in libexec/, bin/<tool> is a 2-line sh launcher
@@ -139,12 +143,14 @@ oracle/_build/chainNet_cpu: $(CSRC)/tools/chainNet.c $(CSRC)/host/gac_net.c \
 
 # A/B probe builds of libgachain with extra compile flags (loaded by the
 # Python binding under GAC_LIB_VARIANT=NAME): make variant NAME=mb7 VFLAGS=-DGAC_TILE_MINB=7
-# (VSRC=DIR: the .hip sources and kernel headers from DIR instead, e.g. an
-# earlier commit's, extracted with git show)
+# (VSRC=DIR: the .hip sources and their headers from DIR instead, e.g. an
+# earlier commit's, extracted with git show -- whichever .hip files DIR holds,
+# so a commit with another set of units builds too)
 VSRC ?= $(CSRC)
 variant: $(HOST_OBJ)
 	@mkdir -p build/variants/$(NAME) $(LIBDIR)/variants/$(NAME)
-	for f in $(notdir $(HIP_SRC)); do $(HIPCC) -I$(VSRC) $(HIPFLAGS) $(VFLAGS) -c $(VSRC)/$$f -o build/variants/$(NAME)/$$(basename $$f .hip).o || exit 1; done
+	rm -f build/variants/$(NAME)/*.o
+	for f in $(VSRC)/*.hip; do $(HIPCC) -I$(VSRC) $(HIPFLAGS) $(VFLAGS) -c $$f -o build/variants/$(NAME)/$$(basename $$f .hip).o || exit 1; done
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(LIBDIR)/variants/$(NAME)/libgachain.so \
 	    build/variants/$(NAME)/*.o $(HOST_OBJ) -Wl,-soname,libgachain.so
 .PHONY: variant

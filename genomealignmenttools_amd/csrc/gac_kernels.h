@@ -1,5 +1,8 @@
 // gac_kernels.h -- device data layout shared by the HIP kernels and the
-// C-ABI implementation (gac_device.hip).  gfx950 only.
+// C-ABI implementation (gac_device.hip and the gac_abi_*.hip units), and the one declaration of
+// every launcher of gac_kernels.hip, gac_compose.hip and gac_axtout.hip (each
+// includes this header, so its definitions are checked against it).  gfx950
+// only.
 //
 // HBM layout (see DESIGN.md "Data layout in HBM"):
 //   genome side (T or Q): 32 bases per "word"
@@ -14,6 +17,7 @@
 //     gap: gapCalcCost to the chain's next block (k_block_gaps_flat, per scoring
 //     setup; 0 after the last block)
 #pragma once
+#include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace gac {
@@ -217,6 +221,23 @@ __host__ __device__ constexpr uint32_t srv_word(uint32_t seq, uint32_t kind, uin
     return (seq & 0xfffffu) | ((n & 0x1ffu) << 20) | ((kind & 1u) << 29);
 }
 
+// Genome upload (k_relayout): one sequence's place in the staged raw .2bit
+// payloads and in the planes.
+struct SeqDev {
+    int64_t byte_off;  // into staging
+    int64_t word_off;  // into planes
+    int32_t size;
+    int32_t pad;
+};
+
+// An N run (or soft-mask run) for k_nruns, pre-split on the host into pieces
+// of <= 1024 bases.
+struct NPiece {
+    int64_t bit0;  // global base index (word_off*32 + start)
+    int32_t len;
+    int32_t pad;
+};
+
 // One run of a sparse genome upload (bytes): its place in the staging layout
 // (8-byte aligned), its offset in the packed upload (8-byte aligned), length.
 struct SparseRun {
@@ -327,5 +348,70 @@ struct AxtCutArgs {
     Window *pieces;       // [P]
     int64_t *first;       // [n + 1]
 };
+
+// ---- launchers and launch helpers of gac_kernels.hip
+int plan_grid(int64_t n);
+int persistent_blocks_per_cu(int which, int sym);
+hipError_t launch_plan(const ScoreArgs &a, hipStream_t s);
+hipError_t launch_tilemap(const ScoreArgs &a, hipStream_t s);
+hipError_t launch_plan_lb(const ScoreArgs &a, hipStream_t s);
+bool plan_lb();
+hipError_t launch_tile(const ScoreArgs &a, int grid, hipStream_t s);
+hipError_t launch_combine(const ScoreArgs &a, int grid, hipStream_t s);
+hipError_t launch_small(const ScoreArgs &a, const Range *rin, SmallOut *out, hipStream_t s);
+hipError_t launch_small_host(const ScoreArgs &a, const RangeDesc *hin, const int4 *pool,
+                             SmallOut *out, hipStream_t s);
+hipError_t launch_small_server(const ScoreArgs &a0, const ScoreArgs &a1, const Range *rin,
+                               const RangeDesc *hin, const int4 *pool, SmallOut *out,
+                               SmallMail *mail, SmallSync *sy, uint32_t last_done, uint64_t idle,
+                               uint32_t trace, int wgs, hipStream_t s);
+hipError_t launch_relayout(const uint8_t *raw, const SeqDev *seqs, int nseq, int64_t nwords,
+                           uint2 *planes, uint32_t *nmask, hipStream_t s);
+hipError_t launch_gap_table(const GapDev &g, const int32_t *small, int len, int32_t *tab,
+                            hipStream_t s);
+hipError_t launch_nruns(const NPiece *p, int64_t n, uint32_t *nmask, hipStream_t s);
+hipError_t launch_build_index(const int32_t *bt, const int32_t *bq, const int32_t *bs, int64_t nb,
+                              const DChain *chains, int64_t n_chains, const int32_t *coff,
+                              const int32_t *tile_c0, int2 *tspan, uint32_t *bucket,
+                              hipStream_t s);
+hipError_t launch_build_flat(const int32_t *bt, const int32_t *bq, const int32_t *bs, int64_t nb,
+                             const DChain *chains, int64_t n_chains, int32_t *coff,
+                             int32_t *tile_c0, int4 *crun, const longlong2 *t_runs,
+                             int64_t n_trun, const longlong2 *q_runs, int64_t n_qrun,
+                             const int64_t *q_woff, int4 *blk, int2 *tspan, uint32_t *bucket,
+                             const UploadGaps &G, bool index, hipStream_t s);
+hipError_t launch_block_gaps_flat(const int32_t *coff, const int32_t *tile_c0, int64_t nb,
+                                  int4 *blk, Blk12 *blk12, const UploadGaps &G, hipStream_t s);
+hipError_t launch_scatter(const SparseRun *runs, int64_t n, const uint64_t *compact,
+                          uint64_t *raw, hipStream_t s);
+hipError_t launch_blocks(const ScoreArgs &a, const BlockJob *jobs, int64_t n, int32_t *out,
+                         hipStream_t s);
+hipError_t launch_whole_plan(const DChain *chains, int64_t n, RangeDesc *rdesc, int32_t *nblk,
+                             int32_t *gflat, int32_t *tile_r0, hipStream_t s);
+hipError_t launch_zero_list(const int32_t *list, int64_t n, long long *g, long long *l,
+                            int32_t *ali, hipStream_t s);
+hipError_t launch_tile_order(const DChain *chains, const int4 *blk, const int32_t *tile_r0,
+                             int64_t T, unsigned long long *keys, int32_t *vals, int32_t *perm,
+                             void *tmp, size_t &tmp_bytes, hipStream_t s);
+hipError_t launch_whole_plan_sorted(const DChain *chains, int64_t n, int32_t *perm,
+                                    unsigned long long *keys, int32_t *vals, RangeDesc *rdesc,
+                                    int32_t *nblk, int32_t *gflat, int32_t *pb0,
+                                    int32_t *tile_r0, int32_t *inv, void *tmp,
+                                    size_t &tmp_bytes, hipStream_t s);
+hipError_t launch_text_blocks(const uint8_t *text, const TextJob *jobs, int64_t n, const M25 &m,
+                              long long *out, hipStream_t s);
+hipError_t launch_text_xover(const uint8_t *text, const TextXJob *jobs, int64_t n, const M25 &m,
+                             int32_t *pos, int32_t *adj, hipStream_t s);
+// ---- gac_compose.hip
+hipError_t launch_compose(const ComposeArgs &a, hipStream_t s);
+hipError_t launch_psl_counts(const PslArgs &a, hipStream_t s);
+// ---- gac_axtout.hip
+hipError_t launch_axt_plan(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_stat(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_place(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_render(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_cut_find(const AxtCutArgs &a, hipStream_t s);
+hipError_t launch_axt_cut_flag(const AxtCutArgs &a, hipStream_t s);
+hipError_t launch_axt_cut_emit(const AxtCutArgs &a, hipStream_t s);
 
 }  // namespace gac

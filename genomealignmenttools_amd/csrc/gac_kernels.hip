@@ -2133,13 +2133,6 @@ __global__ void __launch_bounds__(256) k_small_server(ScoreArgs a0, ScoreArgs a1
 
 // ------------------------------------------------------------ genome -----
 // Raw .2bit payload (2 bits/base, MSB first in each byte) -> bit planes.
-struct SeqDev {
-    int64_t byte_off;  // into staging
-    int64_t word_off;  // into planes
-    int32_t size;
-    int32_t pad;
-};
-
 // 32 codes of 2 bits, MSB first in each byte (8 payload bytes, loaded as one
 // little-endian u64: base 4j + k at bits 8j + 6 - 2k (low bit of the code)
 // and 8j + 7 - 2k (high bit)) -> the low-bit and high-bit planes, base i at
@@ -2228,12 +2221,6 @@ __global__ void __launch_bounds__(256) k_relayout(const uint8_t *raw, const SeqD
 }
 
 // N runs, pre-split on the host into pieces of <= 1024 bases.
-struct NPiece {
-    int64_t bit0;  // global base index (word_off*32 + start)
-    int32_t len;
-    int32_t pad;
-};
-
 __global__ void __launch_bounds__(256) k_nruns(const NPiece *pieces, int64_t n, uint32_t *nmask) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;

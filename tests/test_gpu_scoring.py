@@ -1,6 +1,7 @@
 """GPU parity: libgachain (HIP, gfx950) vs the CPU oracle on the same seeded
 inputs.  Integer scores must be bit-exact (the reference accumulates integer
 addends in double; see include/gachain.h)."""
+import functools
 import os
 
 import numpy as np
@@ -83,6 +84,75 @@ def test_windows_vs_oracle(seed):
             e.score_windows(cs, Wb)
     g, _, a = e.score_windows(cs, W)
     assert np.array_equal(g, og) and np.array_equal(a, oa)
+    cs.close()
+    e.close()
+
+
+_SMALL_MAX = 256  # kSmallMax (gac_kernels.h): batches above it take the staged path
+
+
+def _io_cap(need):
+    """Capacity the host entry points' staging grows to for `need` records."""
+    return need + need // 2 + 1024
+
+
+def _win_units(n):
+    """n 20-byte windows counted in 12-byte range records (gac_score_windows)."""
+    return (20 * n + 11) // 12
+
+
+@functools.lru_cache(maxsize=None)
+def _staging_case():
+    """A few kilobases, a few dozen chains, and more ranges (with their windows
+    and oracle results) than the largest batch of test_host_staging_sizes."""
+    from genomealignmenttools_amd import synth
+    from test_host import subset_windows
+    tg, qg, ca = synth.small_case(seed=9, n_chains=40, tsize=8000, qsizes=(5000, 3000),
+                                  max_blocks=40)
+    rng = np.random.default_rng(9)
+    n = _io_cap(_io_cap(_win_units(_SMALL_MAX + 1)) + 1)  # (above every size used)
+    c = rng.integers(0, ca.n, n)
+    a = rng.integers(ca.tstart[c] - 20, ca.tend[c] + 20)
+    b = rng.integers(ca.tstart[c] - 20, ca.tend[c] + 20)
+    R = np.stack([c, np.minimum(a, b), np.maximum(a, b) + 1], 1).astype(np.int64)
+    first, cnt = subset_windows(ca, R[:, 0], R[:, 1], R[:, 2])
+    W = np.concatenate([R, first[:, None], cnt[:, None]], 1).astype(np.int32)
+    orc = _oracle(tg, qg)
+    full = np.stack([np.arange(ca.n), ca.tstart, ca.tend], 1).astype(np.int64)
+    return tg, qg, ca, R, W, orc.score_ranges(ca, R), orc.score_ranges(ca, full)
+
+
+@pytest.mark.parametrize("want_local", [True, False])
+def test_host_staging_sizes(want_local):
+    """gac_score_windows, gac_score_ranges and gac_score_chains share one set
+    of staging buffers on a context, sized in 12-byte range records; windows
+    are 20 bytes.  One context takes them in turn at the counts where a
+    capacity kept in the wrong unit would show, each equal to the oracle:
+    windows just above the small-batch limit (the first growth, in window
+    units); ranges that exactly fill that capacity (no regrowth) and one more
+    (regrowth); the most windows that still fit that capacity, and one more;
+    whole chains."""
+    tg, qg, ca, R, W, (og, ol, oa), (wg, wl, wa) = _staging_case()
+    n1 = _SMALL_MAX + 1
+    cap1 = _io_cap(_win_units(n1))
+    cap2 = _io_cap(cap1 + 1)
+    n4 = 12 * cap2 // 20
+    assert _win_units(n4) <= cap2 < _win_units(n4 + 1) and n4 + 1 <= len(R)
+    assert n1 < cap1 < n4  # (every batch is above the small-batch limit)
+    e, cs = _setup(None, tg, qg, ca)
+
+    def same(res, n, ref=(og, ol, oa)):
+        g, l, a = res
+        assert np.array_equal(g, ref[0][:n]) and np.array_equal(a, ref[2][:n])
+        if want_local:
+            assert np.array_equal(l, ref[1][:n])
+
+    same(e.score_windows(cs, W[:n1], want_local=want_local), n1)
+    for n in (cap1, cap1 + 1):
+        same(e.score_ranges(cs, R[:n], want_local=want_local), n)
+    for n in (n4, n4 + 1):
+        same(e.score_windows(cs, W[:n], want_local=want_local), n)
+    same(e.score_chains(cs, want_local=want_local), ca.n, (wg, wl, wa))
     cs.close()
     e.close()
 
