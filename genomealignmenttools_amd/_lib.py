@@ -25,7 +25,7 @@ GAC_OK = 0
 GAC_T = 0
 GAC_Q = 1
 GAC_WANT_LOCAL = 1
-GAC_K_PLAN, GAC_K_TILE, GAC_K_COMBINE = 0, 1, 2
+GAC_K_PLAN, GAC_K_TILE, GAC_K_COMBINE, GAC_K_DEPTH = 0, 1, 2, 3
 
 _lock = threading.Lock()
 _lib = None
@@ -156,6 +156,11 @@ _PROTOS = {
     "gac_chain_psl_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gac_chain_psl_counts_device": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gac_depth_count": (
+        C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                  C.c_void_p]),
+    "gac_depth_count_host": (
+        C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "gac_antirepeat_pass": (
         C.c_int, [C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int]),
     "gac_abi_minor": (C.c_int, []),

@@ -1,6 +1,6 @@
 // gac_kernels.h -- device data layout shared by the HIP kernels and the
 // C-ABI implementation (gac_device.hip and the gac_abi_*.hip units), and the one declaration of
-// every launcher of gac_kernels.hip, gac_compose.hip and gac_axtout.hip (each
+// every launcher of gac_kernels.hip, gac_compose.hip, gac_axtout.hip and gac_depth.hip (each
 // includes this header, so its definitions are checked against it).  gfx950
 // only.
 //
@@ -413,5 +413,29 @@ hipError_t launch_axt_render(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_cut_find(const AxtCutArgs &a, hipStream_t s);
 hipError_t launch_axt_cut_flag(const AxtCutArgs &a, hipStream_t s);
 hipError_t launch_axt_cut_emit(const AxtCutArgs &a, hipStream_t s);
+
+// ---- gac_depth.hip: coverage depth of n ranges (gac_depth_count).  Event e
+// < n is the start of range e, event n + i the end of range i; arrays of 2n
+// unless noted.
+struct DepthArgs {
+    int64_t n;
+    int32_t threshold;
+    const int32_t *seq, *start, *end;  // [n]
+    const int8_t *delta;               // [n]
+    unsigned long long *key;           // (seq << 32) | position, by event
+    int32_t *val;                      // the event id, by event
+    const unsigned long long *skey;    // the keys sorted
+    const int32_t *sval;               // the events in that order
+    int32_t *sdelta;                   // their signed deltas
+    int32_t *where;                    // by event: its sorted position
+    const int32_t *excl;               // exclusive scan of sdelta
+    long long *len;                    // covered length from k to k + 1
+    const long long *before;           // exclusive scan of len
+    int32_t *count;                    // [n]
+};
+hipError_t launch_depth_events(const DepthArgs &a, hipStream_t s);
+hipError_t launch_depth_gather(const DepthArgs &a, hipStream_t s);
+hipError_t launch_depth_cover(const DepthArgs &a, hipStream_t s);
+hipError_t launch_depth_out(const DepthArgs &a, hipStream_t s);
 
 }  // namespace gac

@@ -142,6 +142,13 @@ int gac_par_format_buf(int64_t nr, void (*fn)(gac_obuf *o, int64_t r, void *arg)
 int gac_par_format(int64_t nr, void (*fn)(FILE *f, int64_t r, void *arg), void *arg, char ***bufs,
                    size_t **lens);
 
+/* gac_depth_count's argument check (shared with gac_depth_count_host): GAC_OK
+ * or GAC_E_ARG with the message set; *max_seq (may be NULL): the largest
+ * sequence id */
+int gac_depth_check(int64_t n, const int32_t *seq, const int32_t *start, const int32_t *end,
+                    const int8_t *delta, int32_t threshold, const int32_t *count,
+                    int32_t *max_seq);
+
 /* ---- host view of a resident sequence (kept after gac_genome_finalize) ----
  * packed: 2 bits/base MSB-first (T=0 C=1 A=2 G=3); N runs merged and sorted. */
 typedef struct gac_seq_view {

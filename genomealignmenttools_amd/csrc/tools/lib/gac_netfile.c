@@ -5,6 +5,7 @@
 
 #include <ctype.h>
 #include <limits.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <stdatomic.h>
@@ -322,6 +323,388 @@ void gt_netset_free(gt_netset *ns) {
     free(ns->nets);
     free(ns->fills);
     memset(ns, 0, sizeof(*ns));
+}
+
+/* ------------------------------------------------------------ full-field nets */
+/* cnFillFromLine (chainNet.c:86-150) of one line, without touching it and
+ * without aborting: NF_OK, or what the reference (or this tool) complains
+ * about first, in its order of checks */
+enum { NF_OK = 0, NF_WORDS, NF_NUM, NF_NOVAL };
+typedef struct nf_err {
+    int kind, field, wc; /* field: 1-based word (NF_NUM), the name's word (NF_NOVAL) */
+    const char *tok;
+    int tok_len;
+} nf_err;
+
+/* lineFileNeedNum (linefile.c:1015-1025): a '-' or a digit first, then atoi */
+static int ref_num(const char *t, int32_t *v) {
+    if (*t != '-' && !isdigit((unsigned char)*t))
+        return 0;
+    *v = (int32_t)strtol(t, NULL, 10); /* (the token ends at white space or NUL) */
+    return 1;
+}
+
+static int tok_is(const char *t, int len, const char *name) {
+    return (int)strlen(name) == len && memcmp(t, name, (size_t)len) == 0;
+}
+
+static int nfill_parse(const char *line, gt_nfill *f, nf_err *e) {
+    const char *w[64];
+    int wl[64], wc = 0;
+    const char *p = line;
+    while (wc < 64) { /* chopLine: at most 64 words */
+        while (*p && isspace((unsigned char)*p))
+            ++p;
+        if (*p == 0)
+            break;
+        w[wc] = p;
+        while (*p && !isspace((unsigned char)*p))
+            ++p;
+        wl[wc] = (int)(p - w[wc]);
+        ++wc;
+    }
+    e->wc = wc;
+    if (wc < 7)
+        return e->kind = NF_WORDS;
+    f->score = 0;
+    f->chain_id = f->ali = 0;
+    f->qover = f->qfar = f->qdup = f->type = -1;
+    f->tn = f->qn = f->tr = f->qr = f->tnewr = f->qnewr = f->toldr = f->qoldr = f->ttrf = f->qtrf = -1;
+    f->child = f->next = f->parent = -1;
+    f->level = 0;
+    f->qname = -1;
+    f->type_off = f->type_len = 0;
+#define NF_NEED(ix, dst)                 \
+    if (!ref_num(w[ix], dst)) {          \
+        e->field = (ix) + 1;             \
+        e->tok = w[ix];                  \
+        e->tok_len = wl[ix];             \
+        return e->kind = NF_NUM;         \
+    }
+    NF_NEED(1, &f->tstart)
+    NF_NEED(2, &f->tsize)
+    f->q_off = (int32_t)(w[3] - line);
+    f->q_len = wl[3];
+    f->qstrand = w[4][0];
+    NF_NEED(5, &f->qstart)
+    NF_NEED(6, &f->qsize)
+    static const struct {
+        const char *name;
+        size_t off;
+    } k_int[] = {
+        {"id", offsetof(gt_nfill, chain_id)}, {"ali", offsetof(gt_nfill, ali)},
+        {"tN", offsetof(gt_nfill, tn)},       {"qN", offsetof(gt_nfill, qn)},
+        {"tR", offsetof(gt_nfill, tr)},       {"qR", offsetof(gt_nfill, qr)},
+        {"tNewR", offsetof(gt_nfill, tnewr)}, {"qNewR", offsetof(gt_nfill, qnewr)},
+        {"tOldR", offsetof(gt_nfill, toldr)}, {"qOldR", offsetof(gt_nfill, qoldr)},
+        {"tTrf", offsetof(gt_nfill, ttrf)},   {"qTrf", offsetof(gt_nfill, qtrf)},
+        {"qOver", offsetof(gt_nfill, qover)}, {"qFar", offsetof(gt_nfill, qfar)},
+        {"qDup", offsetof(gt_nfill, qdup)},
+    };
+    for (int i = 7; i < wc; i += 2) {
+        if (i + 1 >= wc) { /* the reference reads words[i + 1] all the same */
+            e->field = i + 1;
+            e->tok = w[i];
+            e->tok_len = wl[i];
+            return e->kind = NF_NOVAL;
+        }
+        if (tok_is(w[i], wl[i], "score"))
+            f->score = atof(w[i + 1]);
+        else if (tok_is(w[i], wl[i], "type")) {
+            f->type_off = (int32_t)(w[i + 1] - line);
+            f->type_len = wl[i + 1];
+        } else {
+            int32_t v;
+            NF_NEED(i + 1, &v)
+            for (size_t k = 0; k < sizeof(k_int) / sizeof(k_int[0]); ++k)
+                if (tok_is(w[i], wl[i], k_int[k].name)) {
+                    *(int32_t *)((char *)f + k_int[k].off) = v;
+                    break;
+                }
+        }
+    }
+#undef NF_NEED
+    return e->kind = NF_OK;
+}
+
+static void nfill_abort(const nf_err *e, int64_t line_no, const char *what) {
+    if (e->kind == NF_WORDS)
+        gt_abort("Expecting at least 7 words line %lld of %s got %d", (long long)line_no, what, e->wc);
+    if (e->kind == NF_NUM)
+        gt_abort("Expecting number field %d line %lld of %s, got %.*s", e->field,
+                 (long long)line_no, what, e->tok_len, e->tok);
+    gt_abort("Field %.*s without a value line %lld of %s", e->tok_len, e->tok, (long long)line_no,
+             what);
+}
+
+typedef struct npre_job {
+    const gt_lines *l;
+    gt_nfill *f;
+    int64_t per;
+    _Atomic int64_t next;
+} npre_job;
+
+static void *npre_thread(void *arg) {
+    npre_job *J = arg;
+    for (;;) {
+        const int64_t a = atomic_fetch_add(&J->next, 1) * J->per;
+        if (a >= J->l->n)
+            return NULL;
+        const int64_t b = a + J->per < J->l->n ? a + J->per : J->l->n;
+        for (int64_t i = a; i < b; ++i) {
+            const char *s = J->l->line[i];
+            gt_nfill *x = &J->f[i];
+            const char *q = s;
+            while (isspace((unsigned char)*q)) /* lineFileNextReal */
+                ++q;
+            x->real = *q != 0 && *q != '#';
+            x->lead = lead_spaces(s);
+            nf_err e;
+            x->ok = x->real && x->lead > 0 && nfill_parse(s, x, &e) == NF_OK;
+        }
+    }
+}
+
+typedef struct nreader {
+    const gt_lines *l;
+    int64_t pos; /* lines consumed: the 1-based number of the last one read */
+    const char *what;
+    gt_nnetset *ns;
+} nreader;
+
+static int64_t nnext_real(nreader *r) { /* the line's index or -1 */
+    while (r->pos < r->l->n)
+        if (r->ns->fills[r->pos++].real)
+            return r->pos - 1;
+    return -1;
+}
+
+/* cnFillRead (chainNet.c:152-185): a deeper line opens the child list of the
+ * last record of this list -- replacing a list that record already had, when a
+ * line comes back to a level between the two */
+static int32_t nread_list(nreader *r) {
+    gt_nnetset *ns = r->ns;
+    int depth = 0;
+    int32_t head = -1, tail = -1, fill = -1;
+    for (;;) {
+        const int64_t i = nnext_real(r);
+        if (i < 0)
+            break;
+        gt_nfill *f = &ns->fills[i];
+        const int d = f->lead;
+        if (fill < 0)
+            depth = d;
+        if (d < depth) {
+            --r->pos; /* lineFileReuse */
+            break;
+        }
+        if (d > depth) {
+            --r->pos;
+            const int32_t c = nread_list(r);
+            ns->fills[fill].child = c;
+            continue;
+        }
+        if (!f->ok) { /* a line at level 0, or one the reference refuses */
+            nf_err e;
+            if (nfill_parse(r->l->line[i], f, &e) != NF_OK)
+                nfill_abort(&e, i + 1, r->what);
+        }
+        const char *s = r->l->line[i];
+        f->qname = gt_names_add(ns->qnames, s + f->q_off, (size_t)f->q_len);
+        if (f->type_len)
+            f->type = gt_names_add(ns->types, s + f->type_off, (size_t)f->type_len);
+        fill = (int32_t)i;
+        if (tail < 0)
+            head = fill;
+        else
+            ns->fills[tail].next = fill;
+        tail = fill;
+    }
+    return head;
+}
+
+/* pre-order over a sibling list: level, parent, the output order */
+static void norder(gt_nnetset *ns, int32_t f, int32_t parent, int32_t level) {
+    for (; f >= 0; f = ns->fills[f].next) {
+        ns->fills[f].parent = parent;
+        ns->fills[f].level = level;
+        ns->order[ns->n_order++] = f;
+        if (ns->fills[f].child >= 0)
+            norder(ns, ns->fills[f].child, f, level + 1);
+    }
+}
+
+void gt_nnet_parse(const gt_lines *l, const char *what, gt_nnetset *ns) {
+    memset(ns, 0, sizeof(*ns));
+    if (l->n > INT32_MAX)
+        gt_abort("%s: more than %d lines", what, INT32_MAX);
+    ns->nl = l->n;
+    ns->fills = malloc((size_t)(l->n ? l->n : 1) * sizeof(gt_nfill));
+    ns->order = malloc((size_t)(l->n ? l->n : 1) * sizeof(int32_t));
+    ns->qnames = calloc(1, sizeof(gt_names));
+    ns->types = calloc(1, sizeof(gt_names));
+    if (!ns->fills || !ns->order || !ns->qnames || !ns->types)
+        gt_abort("Out of memory");
+    npre_job J = {l, ns->fills, 8192, 0};
+    atomic_init(&J.next, 0);
+    const int64_t slices = l->n / J.per + 1;
+    gac_run_threads(slices < gt_threads() ? (int)slices : gt_threads(), npre_thread, &J);
+    nreader r = {l, 0, what, ns};
+    int64_t i;
+    while ((i = nnext_real(&r)) >= 0) { /* chainNetRead (chainNet.c:244-264) */
+        const char *line = l->line[i];
+        if (strncmp(line, "net ", 4) != 0)
+            gt_abort("Expecting 'net' first word of line %lld of %s", (long long)r.pos, what);
+        char *w[3];
+        char *copy = strdup(line);
+        const int wc = gac_chop_white(copy, w, 3);
+        if (wc < 3)
+            gt_abort("Expecting at least 3 words line %lld of %s got %d", (long long)r.pos, what, wc);
+        if (ns->n == ns->cap) {
+            ns->cap = ns->cap ? ns->cap * 2 : 64;
+            ns->nets = realloc(ns->nets, (size_t)ns->cap * sizeof(gt_net1));
+        }
+        gt_net1 *n = &ns->nets[ns->n++];
+        n->name = strdup(w[1]);
+        if (!ref_num(w[2], &n->size))
+            gt_abort("Expecting number field 3 line %lld of %s, got %s", (long long)r.pos, what, w[2]);
+        free(copy);
+        n->first = nread_list(&r);
+    }
+    ns->net_off = malloc((size_t)(ns->n + 1) * sizeof(int64_t));
+    for (int32_t k = 0; k < ns->n; ++k) {
+        ns->net_off[k] = ns->n_order;
+        norder(ns, ns->nets[k].first, -1, 1);
+    }
+    ns->net_off[ns->n] = ns->n_order;
+}
+
+void gt_nnetset_free(gt_nnetset *ns) {
+    for (int32_t i = 0; i < ns->n; ++i)
+        free(ns->nets[i].name);
+    free(ns->nets);
+    free(ns->fills);
+    free(ns->order);
+    free(ns->net_off);
+    if (ns->qnames)
+        gt_names_free(ns->qnames);
+    if (ns->types)
+        gt_names_free(ns->types);
+    free(ns->qnames);
+    free(ns->types);
+    memset(ns, 0, sizeof(*ns));
+}
+
+/* ---- the typed-net writer */
+typedef struct nwrite_job {
+    const gt_nnetset *ns;
+    const int32_t *qdup;
+    const int32_t *item;   /* >= 0: position in order; < 0: ~net */
+    const size_t *qlen;    /* by query name id */
+} nwrite_job;
+
+static char *put_field(char *p, const char *name, size_t nl, int32_t v) {
+    return gt_put_int(gt_put_str(p, name, nl), v);
+}
+
+static void nwrite_item(FILE *out, int64_t i, void *arg) {
+    const nwrite_job *J = arg;
+    const gt_nnetset *ns = J->ns;
+    const int32_t it = J->item[i];
+    if (it < 0) { /* chainNetWrite (chainNet.c:237-242) */
+        fprintf(out, "net %s %d\n", ns->nets[~it].name, ns->nets[~it].size);
+        return;
+    }
+    const gt_nfill *f = &ns->fills[ns->order[it]];
+    int32_t qover = f->qover, qfar = f->qfar, qdup = f->qdup;
+    const char *type = f->type >= 0 ? ns->types->names[f->type] : NULL;
+    if (f->chain_id) { /* rNetSyn (netSyntenic.c:235-267) */
+        qdup = J->qdup[it];
+        const gt_nfill *par = f->parent >= 0 ? &ns->fills[f->parent] : NULL;
+        if (!par)
+            type = "top";
+        else if (par->qname != f->qname)
+            type = "nonSyn";
+        else {
+            const int64_t fs = f->qstart, fe = fs + f->qsize, ps = par->qstart, pe = ps + par->qsize;
+            const int64_t x = (fe < pe ? fe : pe) - (fs > ps ? fs : ps); /* rangeIntersection */
+            qover = x > 0 ? (int32_t)x : 0;
+            qfar = x > 0 ? 0 : (int32_t)-x;
+            type = par->qstrand == f->qstrand ? "syn" : "inv";
+        }
+    }
+    /* cnFillWrite (chainNet.c:187-235), one level of indentation per nesting level */
+    const char *qn = ns->qnames->names[f->qname];
+    const size_t tl = type ? strlen(type) : 0, need = (size_t)f->level + J->qlen[f->qname] + tl + 1024;
+    char small[2048], *buf = need <= sizeof(small) ? small : malloc(need), *p = buf;
+    memset(p, ' ', (size_t)f->level);
+    p += f->level;
+    p = f->chain_id ? gt_put_str(p, "fill", 4) : gt_put_str(p, "gap", 3);
+    p = gt_put_int(p, f->tstart);
+    p = gt_put_int(p, f->tsize);
+    p = gt_put_str(p, qn, J->qlen[f->qname]);
+    *p++ = f->qstrand;
+    *p++ = ' ';
+    p = gt_put_int(p, f->qstart);
+    p = gt_put_int(p, f->qsize);
+    if (f->chain_id)
+        p = put_field(p, "id", 2, f->chain_id);
+    if (f->score > 0) {
+        p = gt_put_str(p, "score", 5);
+        if (f->score < 9007199254740992.0 && f->score == (double)(int64_t)f->score)
+            p = gt_put_int(p, (int64_t)f->score);
+        else /* (at most 309 digits) */
+            p += snprintf(p, 400, "%1.0f ", f->score);
+    }
+    if (f->ali > 0)
+        p = put_field(p, "ali", 3, f->ali);
+    if (qover >= 0)
+        p = put_field(p, "qOver", 5, qover);
+    if (qfar >= 0)
+        p = put_field(p, "qFar", 4, qfar);
+    if (qdup >= 0)
+        p = put_field(p, "qDup", 4, qdup);
+    if (type)
+        p = gt_put_str(gt_put_str(p, "type", 4), type, tl);
+    static const struct {
+        const char *name;
+        size_t nl, off;
+    } k_tail[] = {
+        {"tN", 2, offsetof(gt_nfill, tn)},       {"qN", 2, offsetof(gt_nfill, qn)},
+        {"tR", 2, offsetof(gt_nfill, tr)},       {"qR", 2, offsetof(gt_nfill, qr)},
+        {"tNewR", 5, offsetof(gt_nfill, tnewr)}, {"qNewR", 5, offsetof(gt_nfill, qnewr)},
+        {"tOldR", 5, offsetof(gt_nfill, toldr)}, {"qOldR", 5, offsetof(gt_nfill, qoldr)},
+        {"tTrf", 4, offsetof(gt_nfill, ttrf)},   {"qTrf", 4, offsetof(gt_nfill, qtrf)},
+    };
+    for (size_t k = 0; k < sizeof(k_tail) / sizeof(k_tail[0]); ++k) {
+        const int32_t v = *(const int32_t *)((const char *)f + k_tail[k].off);
+        if (v >= 0)
+            p = put_field(p, k_tail[k].name, k_tail[k].nl, v);
+    }
+    p[-1] = '\n'; /* every piece above ends in one space */
+    fwrite(buf, 1, (size_t)(p - buf), out);
+    if (buf != small)
+        free(buf);
+}
+
+void gt_nnet_write_typed(FILE *out, const gt_nnetset *ns, const int32_t *qdup) {
+    const int64_t n = ns->n + ns->n_order;
+    int32_t *item = malloc((size_t)(n ? n : 1) * sizeof(int32_t));
+    size_t *qlen = malloc((size_t)(ns->qnames->n ? ns->qnames->n : 1) * sizeof(size_t));
+    if (!item || !qlen)
+        gt_abort("Out of memory");
+    for (int32_t q = 0; q < ns->qnames->n; ++q)
+        qlen[q] = strlen(ns->qnames->names[q]);
+    int64_t m = 0;
+    for (int32_t k = 0; k < ns->n; ++k) {
+        item[m++] = ~k;
+        for (int64_t o = ns->net_off[k]; o < ns->net_off[k + 1]; ++o)
+            item[m++] = (int32_t)o;
+    }
+    nwrite_job J = {ns, qdup, item, qlen};
+    gt_par_write(out, n, nwrite_item, &J);
+    free(item);
+    free(qlen);
 }
 
 /* ------------------------------------------------------------ NetFilterNonNested */

@@ -9,6 +9,7 @@
 #define GAC_NETFILE_H
 
 #include <stdint.h>
+#include <stdio.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -49,6 +50,54 @@ typedef struct gt_netset {
  * lineFileNextReal).  `what` names the source in error messages. */
 void gt_net_parse(const gt_lines *l, const char *what, gt_netset *ns);
 void gt_netset_free(gt_netset *ns);
+
+/* ---- nets with every field the reference keeps (netSyntenic) ----
+ * cnFillFromLine's record (kent/src/hg/lib/chainNet.c:86-150) in full; absent
+ * integer fields are -1, ali and score 0, type -1.  A record is the line it
+ * came from: fills[i] belongs to line i of the text (lines that are no record
+ * leave theirs unused), so child / next / parent are line indices (-1: none).
+ * parent is the enclosing record, the `parent` of rNetSyn
+ * (kent/src/hg/mouseStuff/netSyntenic/netSyntenic.c:227-271). */
+typedef struct gt_nfill {
+    int32_t tstart, tsize;
+    int32_t qname; /* id in gt_nnetset.qnames: one table for the whole file */
+    int32_t qstart, qsize;
+    int32_t chain_id; /* 0 = gap */
+    double score;
+    int32_t ali, qover, qfar, qdup;
+    int32_t type; /* id in gt_nnetset.types */
+    int32_t tn, qn, tr, qr, tnewr, qnewr, toldr, qoldr, ttrf, qtrf;
+    int32_t child, next, parent;
+    int32_t level; /* nesting level (1: top), what chainNetWrite indents by */
+    char qstrand;
+    /* the parallel pre-pass's notes on the line (gt_nnet_parse) */
+    uint8_t real, ok;
+    int32_t lead, q_off, q_len, type_off, type_len;
+} gt_nfill;
+
+typedef struct gt_nnetset {
+    gt_net1 *nets; /* first: line index of the first top-level record */
+    int32_t n, cap;
+    gt_nfill *fills; /* [lines] */
+    int64_t nl;
+    struct gt_names *qnames, *types;
+    /* the records of the trees in chainNetWrite's order (pre-order), net by
+     * net: order[net_off[k] .. net_off[k + 1]) are net k's */
+    int32_t *order;
+    int64_t n_order, *net_off;
+} gt_nnetset;
+
+/* chainNetRead of the whole text, with its error messages (a field name
+ * without a value, which the reference reads past the line's words, aborts
+ * with a message of this tool's own).  Lines are parsed on all threads first,
+ * the trees are linked in one serial pass. */
+void gt_nnet_parse(const gt_lines *l, const char *what, gt_nnetset *ns);
+void gt_nnetset_free(gt_nnetset *ns);
+/* netSyntenic's output of the nets (rNetSyn + chainNetWrite): every fill gets
+ * qDup = qdup[its position in order], its type and, for syn / inv, qOver and
+ * qFar from its parent; the other fields and the gaps are written as read.
+ * Formatted by gt_par_write's workers. */
+void gt_nnet_write_typed(FILE *out, const gt_nnetset *ns, const int32_t *qdup);
 
 /* NetFilterNonNested.perl "12" mode: keep a fill if (score >= s1 && tSize >=
  * t1 && qSize >= q1) || (score >= s2 && tSize >= t2 && qSize >= q2); the gaps

@@ -179,9 +179,10 @@ static void *device_thread(void *arg) {
     memset(&P, 0, sizeof(P));
     P.path[0] = d->t2bit;
     P.path[1] = d->q2bit;
+    const int genomes = d->t2bit != NULL; /* (gt_device_start_bare: the context only) */
     pthread_t pre;
-    const int pre_ok = pthread_create(&pre, NULL, twobit_pre_thread, &P) == 0;
-    if (!pre_ok)
+    const int pre_ok = genomes && pthread_create(&pre, NULL, twobit_pre_thread, &P) == 0;
+    if (genomes && !pre_ok)
         twobit_pre_thread(&P);
     int rc = gac_open(g_gpu, &d->ctx);
     d->open_s = gt_now_s() - t0;
@@ -191,7 +192,7 @@ static void *device_thread(void *arg) {
         rc = g_open_hook(d->ctx);
     if (pre_ok)
         pthread_join(pre, NULL);
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; genomes && k < 2; ++k) {
         if (rc == GAC_OK && P.rc[k] != GAC_OK) {
             rc = P.rc[k];
             snprintf(d->err, sizeof(d->err), "%s", P.err[k]);
@@ -454,6 +455,8 @@ void gt_device_start(gt_device *d, const char *t2bit, const char *q2bit, const i
                      const gac_gapcalc *gap) {
     gt_device_start_ex(d, t2bit, q2bit, mat, gap, NULL, NULL);
 }
+
+void gt_device_start_bare(gt_device *d) { gt_device_start_ex(d, NULL, NULL, NULL, NULL, NULL, NULL); }
 
 void gt_device_start_keep(gt_device *d, const char *t2bit, const char *q2bit,
                           const int32_t mat[16], const gac_gapcalc *gap, const gt_names *tkeep) {

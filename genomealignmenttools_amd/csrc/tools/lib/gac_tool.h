@@ -78,6 +78,9 @@ typedef struct gt_device {
 } gt_device;
 void gt_device_start(gt_device *d, const char *t2bit, const char *q2bit, const int32_t mat[16],
                      const gac_gapcalc *gap);
+/* the context only: no genomes, no scoring setup (netSyntenic's depth count
+ * needs neither) */
+void gt_device_start_bare(gt_device *d);
 /* chainNet -rescore: compute the word runs under the blocks of c's chains
  * for the two .2bit files (on a helper thread) and publish them to R; the
  * device thread of a gt_device whose runs == R waits for them */

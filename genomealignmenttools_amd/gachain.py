@@ -13,6 +13,8 @@ twoBitReadSeqFragExt(doMask) (twoBit.c:835)  Engine.load_2bit(..., soft_mask=Tru
 chainAntiRepeat's two filters' counts        Engine.chain_composition(chainset)
   (chainAntiRepeat.c:40-117) and decision    antirepeat_pass(score, match, rep, total, minScore)
 chainToPsl's four counts (chainToPsl.c:106)  Engine.chain_psl_counts(chainset)
+netSyntenic's dupeTree (netSyntenic.c:63)    Engine.depth_count(seq, start, end, delta, threshold)
+                                             depth_count_host(...): the same on the CPU
 axtScoreUngapped per block (axt.c:186-194)   Engine.score_blocks / score_text_blocks (caller text)
 cBlockFindCrossover (chainConnect.c:61-105)  Engine.crossovers / text_crossovers (caller text)
 chainBlocks' kd-tree DP (chainBlock.c:400)   Engine.chain_dp_blocks (total, predecessor per block)
@@ -197,6 +199,18 @@ class Engine:
     def chain_psl_counts_device(self, cs: "ChainSet", d_counts: int, stream: int = 0) -> None:
         check(lib().gac_chain_psl_counts_device(
             self.h, cs.handle, C.c_void_p(d_counts), C.c_void_p(stream) if stream else None))
+
+    # ---- coverage depth (netSyntenic)
+    def depth_count(self, seq, start, end, delta, threshold: int = 2) -> np.ndarray:
+        """Per range [start, end) of sequence seq: the positions whose summed
+        depth (delta of every range of that sequence covering them) is >=
+        threshold (gac_depth_count): int32 [n].  netSyntenic's qDup with
+        delta +1 for fills, -1 for gaps, threshold 2."""
+        a = _depth_args(seq, start, end, delta)
+        count = np.zeros(len(a[0]), np.int32)
+        check(lib().gac_depth_count(self.h, len(a[0]), _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]),
+                                    int(threshold), _p(count)))
+        return count
 
     # ---- alignment text (chainToAxt)
     @staticmethod
@@ -525,6 +539,23 @@ class Engine:
         return ms.value, n.value
 
 
+def _depth_args(seq, start, end, delta):
+    a = [np.ascontiguousarray(x, dtype=t)
+         for x, t in ((seq, np.int32), (start, np.int32), (end, np.int32), (delta, np.int8))]
+    if any(x.ndim != 1 or len(x) != len(a[0]) for x in a):
+        raise ValueError("depth_count: seq, start, end and delta must be 1-d and of one length")
+    return a
+
+
+def depth_count_host(seq, start, end, delta, threshold: int = 2) -> np.ndarray:
+    """Engine.depth_count's result on the CPU (gac_depth_count_host; no device)."""
+    a = _depth_args(seq, start, end, delta)
+    count = np.zeros(len(a[0]), np.int32)
+    check(lib().gac_depth_count_host(len(a[0]), _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]),
+                                     int(threshold), _p(count)))
+    return count
+
+
 def antirepeat_pass(score: float, match, rep: int, total: int, min_score: int = 5000) -> bool:
     """chainAntiRepeat's keep/drop decision for one chain from its composition
     (gac_antirepeat_pass: degeneracyFilter then repeatFilter; host only)."""
@@ -545,4 +576,4 @@ def twobit_mask_runs(path: str, name: str) -> Tuple[np.ndarray, np.ndarray]:
 
 
 __all__ = ["Engine", "ChainSet", "GapCosts", "read_score_scheme", "GAC_T", "GAC_Q",
-           "antirepeat_pass", "twobit_mask_runs"]
+           "antirepeat_pass", "twobit_mask_runs", "depth_count_host"]

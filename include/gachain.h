@@ -59,8 +59,9 @@ extern "C" {
  * 1 = the alignment text entry points (gac_axt_*).
  * 2 = gac_axt_cut and the clip-aware gac_axt_*_clip entry points (netToAxt).
  * 3 = gac_chain_psl_counts[_device] (chainToPsl).
- * 4 = gac_net_write_ex and gac_net_release (chainNet frees a net under its writers). */
-#define GAC_ABI_MINOR 4
+ * 4 = gac_net_write_ex and gac_net_release (chainNet frees a net under its writers).
+ * 5 = gac_depth_count and gac_depth_count_host (netSyntenic). */
+#define GAC_ABI_MINOR 5
 
 /* return codes */
 #define GAC_OK 0
@@ -336,6 +337,25 @@ int gac_chain_psl_counts(gac_ctx *ctx, const gac_chainset *cs, int64_t *counts);
  * (NULL: the context's); returns once enqueued. */
 int gac_chain_psl_counts_device(gac_ctx *ctx, const gac_chainset *cs, int64_t *d_counts,
                                 void *stream);
+
+/* ---- coverage depth of ranges (netSyntenic) --------------------------------
+ * count[i] = the number of positions p in [start[i], end[i]) of sequence
+ * seq[i] at which the summed depth, sum over j of delta[j] where seq[j] ==
+ * seq[i] and start[j] <= p < end[j], is >= threshold.  With delta +1 for a
+ * fill's query range, -1 for a gap's and threshold 2 this is netSyntenic's qDup
+ * (dupeTreeAddSub / dupeTreeCountOver,
+ * kent/src/hg/mouseStuff/netSyntenic/netSyntenic.c:63-138) for every range at
+ * once; ranges of length 0 count 0.  Sequence ids are any non-negative
+ * numbers (sparse is fine).  Exact integers.  GAC_E_ARG: end < start, a
+ * negative seq or start, threshold < 1, or more than INT32_MAX / 2 ranges.
+ * n == 0 returns GAC_OK without a launch.  Host buffers, synchronous; needs
+ * neither genomes nor a scoring setup. */
+int gac_depth_count(gac_ctx *ctx, int64_t n, const int32_t *seq, const int32_t *start,
+                    const int32_t *end, const int8_t *delta, int32_t threshold, int32_t *count);
+/* The same result without a device: a threaded sort of the range ends and
+ * one sweep (netSyntenic -host). */
+int gac_depth_count_host(int64_t n, const int32_t *seq, const int32_t *start, const int32_t *end,
+                         const int8_t *delta, int32_t threshold, int32_t *count);
 
 /* ---- alignment text (chainToAxt) ------------------------------------------
  * A piece is a window of consecutive blocks of one chain (gac_window: chain,
@@ -798,7 +818,8 @@ int gac_synchronize(gac_ctx *ctx);
 #define GAC_K_PLAN 0     /* block-window search + scans + tile map (k_plan, k_tilemap_fused or k_scan_agg + k_tilemap) */
 #define GAC_K_TILE 1     /* tile scoring: bases, gaps, per-tile scan (dominant) */
 #define GAC_K_COMBINE 2  /* multi-tile range combine */
-#define GAC_K_COUNT 3
+#define GAC_K_DEPTH 3    /* gac_depth_count: events, sort, scans, counts (one lap per call) */
+#define GAC_K_COUNT 4
 #define GAC_PROF_ALL ((1 << GAC_K_COUNT) - 1)
 /* Event timing of each launch of the kernels in `mask` (bits 1 << GAC_K_*;
  * 0 = off, GAC_PROF_ALL = all).  Each timed kernel adds two event markers
