@@ -272,6 +272,8 @@ _PROTOS = {
     "gac_chain_dp_blocks": (
         C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 6 +
         [C.c_int, C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "gac_kd_trees": (
+        C.c_int, [C.c_void_p, C.c_int64] + [C.c_void_p] * 10),
     "gac_score_text_blocks": (
         C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                   C.POINTER(C.c_int32), C.c_void_p]),

@@ -299,12 +299,13 @@ __global__ void __launch_bounds__(kDtThreads)
     int32_t n = 0;
     bool ovf = false;
     // target side: the leaves before it in target order starting within m
+    // that overlap it on the target (one overlapping on the query only may
+    // start within m too: the q scan lists it, once)
     for (int64_t j = i - 1; j >= lo_i; --j) {
         const int4 b = lf[j];
         if (!(b.z > lt - m)) break;
         if (b.z >= lt || b.x >= lq) continue;
-        const int32_t dq = lq - b.y, dt = lt - b.w;
-        if (dq >= 0 && dt >= 0) continue;
+        if (lt - b.w >= 0) continue;
         if (n == cap) {
             ovf = true;
             break;

@@ -489,6 +489,29 @@ class Engine:
                                         _p(total), _p(pred)))
         return leaf_off, tord[:int(leaf_off[-1])], total, pred
 
+    def kd_trees(self, t_seq, q_seq, q_strand, blk_off, box):
+        """kdTreeMake of n pairs from their blocks (gac_kd_trees).  Returns
+        (leaf_off int64 [n + 1], and per pair lists of int32 arrays: tord[p],
+        qord[p] (its leaves' pair-local blocks in target / query order),
+        lnode[p] (per block its leaf node, -1: no leaf), nodes[p] [2 leaves - 1,
+        6] in pre-order with the hi child first)."""
+        a = [np.ascontiguousarray(t_seq, np.int32), np.ascontiguousarray(q_seq, np.int32),
+             np.ascontiguousarray(q_strand, np.uint8), np.ascontiguousarray(blk_off, np.int64),
+             np.ascontiguousarray(np.asarray(box, np.int32).reshape(-1, 4))]
+        n = len(a[0])
+        cnt = np.diff(a[3]) if n else np.zeros(0, np.int64)
+        cap = [max(int(c), 0) for c in cnt]  # (descending offsets are the call's to refuse)
+        leaf_off = np.zeros(n + 1, np.int64)
+        bufs = [[np.full(max(w * c, 1), -9, np.int32) for c in cap] for w in (1, 1, 1, 12)]
+        ptrs = [(C.c_void_p * max(n, 1))(*[b.ctypes.data for b in col]) for col in bufs]
+        check(lib().gac_kd_trees(self.h, n, *[_p(x) for x in a], _p(leaf_off), *ptrs))
+        nl = np.diff(leaf_off).astype(np.int64)
+        tord = [bufs[0][p][:nl[p]] for p in range(n)]
+        qord = [bufs[1][p][:nl[p]] for p in range(n)]
+        lnode = [bufs[2][p][:cap[p]] for p in range(n)]
+        nodes = [bufs[3][p][:6 * max(2 * nl[p] - 1, 0)].reshape(-1, 6) for p in range(n)]
+        return leaf_off, tord, qord, lnode, nodes
+
     # ---- device buffers / timing (bench)
     def dev_alloc(self, nbytes: int) -> int:
         p = C.c_void_p()

@@ -857,7 +857,7 @@ int gac_chain_dp_blocks(gac_ctx *c, int64_t P, const int32_t *t_seq, const int32
                     break;
                 if (b[2] >= lt || b[0] >= lq)
                     continue;
-                if (lq - b[1] >= 0 && lt - b[3] >= 0)
+                if (lt - b[3] >= 0) /* (overlapping on the query only: the q scan's) */
                     continue;
                 if (n == ov_cap)
                     ovf = 1;
