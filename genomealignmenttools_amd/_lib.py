@@ -25,7 +25,9 @@ GAC_OK = 0
 GAC_T = 0
 GAC_Q = 1
 GAC_WANT_LOCAL = 1
-GAC_K_PLAN, GAC_K_TILE, GAC_K_COMBINE, GAC_K_DEPTH = 0, 1, 2, 3
+GAC_K_PLAN, GAC_K_TILE, GAC_K_COMBINE, GAC_K_DEPTH, GAC_K_PRENET = 0, 1, 2, 3, 4
+GAC_PRENET_MAX_ROUNDS = 32
+GAC_PRENET_ON_DEVICE, GAC_PRENET_FELL_ROUNDS, GAC_PRENET_FELL_MEMORY = 0, 1, 2
 
 _lock = threading.Lock()
 _lib = None
@@ -109,6 +111,11 @@ class AxtChains(C.Structure):
                 ("blk_q", C.POINTER(C.c_int32)), ("blk_size", C.POINTER(C.c_int32))]
 
 
+class PrenetStats(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("passes", C.c_int32), ("groups", C.c_int32 * 2),
+                ("fell_back", C.c_int32), ("pad_", C.c_int32), ("kept", C.c_int64)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "gac_abi_version": (C.c_int, []),
@@ -161,6 +168,14 @@ _PROTOS = {
                   C.c_void_p]),
     "gac_depth_count_host": (
         C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "gac_prenet_keep": (
+        C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                  C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                  C.c_int32, C.c_void_p, C.c_void_p]),
+    "gac_prenet_keep_host": (
+        C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                  C.c_void_p]),
     "gac_antirepeat_pass": (
         C.c_int, [C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int]),
     "gac_abi_minor": (C.c_int, []),

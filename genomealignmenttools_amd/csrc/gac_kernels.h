@@ -1,8 +1,8 @@
 // gac_kernels.h -- device data layout shared by the HIP kernels and the
 // C-ABI implementation (gac_device.hip and the gac_abi_*.hip units), and the one declaration of
-// every launcher of gac_kernels.hip, gac_compose.hip, gac_axtout.hip and gac_depth.hip (each
-// includes this header, so its definitions are checked against it).  gfx950
-// only.
+// every launcher of gac_kernels.hip, gac_compose.hip, gac_axtout.hip, gac_depth.hip and
+// gac_prenet.hip (each includes this header, so its definitions are checked against it).
+// gfx950 only.
 //
 // HBM layout (see DESIGN.md "Data layout in HBM"):
 //   genome side (T or Q): 32 bases per "word"
@@ -437,5 +437,42 @@ hipError_t launch_depth_events(const DepthArgs &a, hipStream_t s);
 hipError_t launch_depth_gather(const DepthArgs &a, hipStream_t s);
 hipError_t launch_depth_cover(const DepthArgs &a, hipStream_t s);
 hipError_t launch_depth_out(const DepthArgs &a, hipStream_t s);
+
+// ---- gac_prenet.hip: chainPreNet's keep decision (gac_prenet_keep).  A pass
+// works on one side (0 target, 1 query) and one group of its sequences: the
+// words fc[sbase[seq] + position] of the group's sequences hold the lowest
+// rank (chain index) that covers the base, kPrenetNone = nothing.
+constexpr uint32_t kPrenetNone = 0xffffffffu;
+constexpr uint8_t kPrenetUndecided = 0, kPrenetKept = 1, kPrenetDropped = 2, kPrenetSkipped = 3;
+struct PrenetArgs {
+    int64_t n, nb;                // chains, blocks
+    int32_t pad;
+    int32_t side, group;          // this pass
+    int32_t with_undecided;       // the covering set: 1 = kept and undecided chains, 0 = kept only
+    const int64_t *boff;          // [n + 1]
+    const int32_t *seq[2];        // [n] per side, -1 = skipped
+    const int32_t *bstart[2];     // [nb] per side
+    const int32_t *bsize;         // [nb]
+    int32_t *bchain;              // [nb] the chain of every block
+    const int32_t *ssize[2];      // per side [sequences]
+    const int32_t *sgroup[2];     // the group of every sequence (-1: no counted chain names it)
+    const int64_t *sbase[2];      // its first word in its group's fc
+    uint8_t *state;               // [n] kPrenet*
+    uint8_t *open;                // [n] 1 = an open base found in this pass
+    long long *len;               // [nb + 1] flat bases of every block in this step (0: not in it)
+    const long long *off;         // [nb + 1] their exclusive scan; off[nb] = the total
+    long long *badr;              // [nb] the fc word of a block's first flat base in this step
+    uint32_t *fc;
+    unsigned long long *counts;   // [2] chains left undecided, chains kept (k_prenet_decide adds)
+};
+hipError_t launch_prenet_setup(const PrenetArgs &a, hipStream_t s);
+// the flat lengths of the covering chains' padded blocks / the undecided chains' blocks
+hipError_t launch_prenet_len(const PrenetArgs &a, bool mark, hipStream_t s);
+hipError_t launch_prenet_mark(const PrenetArgs &a, hipStream_t s);
+hipError_t launch_prenet_check(const PrenetArgs &a, hipStream_t s);
+// after a round's first pass: open undecided chains are kept; after its second:
+// undecided chains that are not open are dropped, and the counts are added up
+hipError_t launch_prenet_decide(const PrenetArgs &a, int pass, hipStream_t s);
+hipError_t launch_prenet_flags(const PrenetArgs &a, uint8_t *keep, hipStream_t s);
 
 }  // namespace gac

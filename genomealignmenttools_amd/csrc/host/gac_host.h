@@ -149,6 +149,13 @@ int gac_depth_check(int64_t n, const int32_t *seq, const int32_t *start, const i
                     const int8_t *delta, int32_t threshold, const int32_t *count,
                     int32_t *max_seq);
 
+/* gac_prenet_keep's argument check (shared with gac_prenet_keep_host): GAC_OK
+ * or GAC_E_ARG with the message set */
+int gac_prenet_check(int64_t n, const int64_t *blk_off, const int32_t *t_seq, const int32_t *q_seq,
+                     int64_t n_blocks, const int32_t *blk_t, const int32_t *blk_q,
+                     const int32_t *blk_size, int32_t n_tseq, const int32_t *t_sizes,
+                     int32_t n_qseq, const int32_t *q_sizes, int32_t pad, const uint8_t *keep);
+
 /* ---- host view of a resident sequence (kept after gac_genome_finalize) ----
  * packed: 2 bits/base MSB-first (T=0 C=1 A=2 G=3); N runs merged and sorted. */
 typedef struct gac_seq_view {

@@ -15,6 +15,8 @@ chainAntiRepeat's two filters' counts        Engine.chain_composition(chainset)
 chainToPsl's four counts (chainToPsl.c:106)  Engine.chain_psl_counts(chainset)
 netSyntenic's dupeTree (netSyntenic.c:63)    Engine.depth_count(seq, start, end, delta, threshold)
                                              depth_count_host(...): the same on the CPU
+chainPreNet's chainUsed (chainPreNet.c:104)  Engine.prenet_keep(blk_off, t_seq, q_seq, ...)
+                                             prenet_keep_host(...): the reference's own pass
 axtScoreUngapped per block (axt.c:186-194)   Engine.score_blocks / score_text_blocks (caller text)
 cBlockFindCrossover (chainConnect.c:61-105)  Engine.crossovers / text_crossovers (caller text)
 chainBlocks' kd-tree DP (chainBlock.c:400)   Engine.chain_dp_blocks (total, predecessor per block)
@@ -211,6 +213,22 @@ class Engine:
         check(lib().gac_depth_count(self.h, len(a[0]), _p(a[0]), _p(a[1]), _p(a[2]), _p(a[3]),
                                     int(threshold), _p(count)))
         return count
+
+    # ---- chains worth netting (chainPreNet)
+    def prenet_keep(self, blk_off, t_seq, q_seq, blk_t, blk_q, blk_size, t_sizes, q_sizes,
+                    pad: int = 1, max_rounds: int = _lib.GAC_PRENET_MAX_ROUNDS):
+        """Which chains chainPreNet writes (gac_prenet_keep): chains in file
+        order with their block offsets [n + 1] and target / query sequence
+        numbers (-1: skipped), blocks with their raw target and query starts
+        and sizes, the sequence sizes per side.  Returns (keep uint8 [n],
+        stats): rounds, passes, groups (target, query), fell_back, kept."""
+        a = _prenet_args(blk_off, t_seq, q_seq, blk_t, blk_q, blk_size, t_sizes, q_sizes)
+        keep = np.zeros(len(a[1]), np.uint8)
+        st = _lib.PrenetStats()
+        check(lib().gac_prenet_keep(self.h, len(a[1]), _p(a[0]), _p(a[1]), _p(a[2]), len(a[3]),
+                                    _p(a[3]), _p(a[4]), _p(a[5]), len(a[6]), _p(a[6]), len(a[7]),
+                                    _p(a[7]), int(pad), int(max_rounds), _p(keep), C.byref(st)))
+        return keep, _prenet_stats(st)
 
     # ---- alignment text (chainToAxt)
     @staticmethod
@@ -579,6 +597,35 @@ def depth_count_host(seq, start, end, delta, threshold: int = 2) -> np.ndarray:
     return count
 
 
+def _prenet_args(blk_off, t_seq, q_seq, blk_t, blk_q, blk_size, t_sizes, q_sizes):
+    a = [np.ascontiguousarray(x, dtype=t)
+         for x, t in ((blk_off, np.int64), (t_seq, np.int32), (q_seq, np.int32), (blk_t, np.int32),
+                      (blk_q, np.int32), (blk_size, np.int32), (t_sizes, np.int32),
+                      (q_sizes, np.int32))]
+    if any(x.ndim != 1 for x in a) or len(a[2]) != len(a[1]) or len(a[0]) != len(a[1]) + 1 or \
+            len(a[4]) != len(a[3]) or len(a[5]) != len(a[3]):
+        raise ValueError("prenet_keep: blk_off [n + 1], t_seq and q_seq [n], blk_t, blk_q and "
+                         "blk_size of one length, all 1-d")
+    return a
+
+
+def _prenet_stats(st) -> dict:
+    return dict(rounds=st.rounds, passes=st.passes, groups=(st.groups[0], st.groups[1]),
+                fell_back=st.fell_back, kept=st.kept)
+
+
+def prenet_keep_host(blk_off, t_seq, q_seq, blk_t, blk_q, blk_size, t_sizes, q_sizes, pad: int = 1):
+    """Engine.prenet_keep's result by the reference's sequential bitmap pass
+    (gac_prenet_keep_host; no device): (keep uint8 [n], stats)."""
+    a = _prenet_args(blk_off, t_seq, q_seq, blk_t, blk_q, blk_size, t_sizes, q_sizes)
+    keep = np.zeros(len(a[1]), np.uint8)
+    st = _lib.PrenetStats()
+    check(lib().gac_prenet_keep_host(len(a[1]), _p(a[0]), _p(a[1]), _p(a[2]), len(a[3]), _p(a[3]),
+                                     _p(a[4]), _p(a[5]), len(a[6]), _p(a[6]), len(a[7]), _p(a[7]),
+                                     int(pad), _p(keep), C.byref(st)))
+    return keep, _prenet_stats(st)
+
+
 def antirepeat_pass(score: float, match, rep: int, total: int, min_score: int = 5000) -> bool:
     """chainAntiRepeat's keep/drop decision for one chain from its composition
     (gac_antirepeat_pass: degeneracyFilter then repeatFilter; host only)."""
@@ -599,4 +646,4 @@ def twobit_mask_runs(path: str, name: str) -> Tuple[np.ndarray, np.ndarray]:
 
 
 __all__ = ["Engine", "ChainSet", "GapCosts", "read_score_scheme", "GAC_T", "GAC_Q",
-           "antirepeat_pass", "twobit_mask_runs", "depth_count_host"]
+           "antirepeat_pass", "twobit_mask_runs", "depth_count_host", "prenet_keep_host"]

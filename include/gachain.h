@@ -41,6 +41,8 @@
  *   gac_axt_*_clip        <- chainFastSubsetOnT's clipped first and last block
  *                                                 kent/src/lib/chain.c:513-522
  *                          (writeChainPart, kent/src/hg/mouseStuff/netToAxt/netToAxt.c:76-105)
+ *   gac_prenet_keep       <- chainUsed + setWithPad
+ *                                                 kent/src/hg/mouseStuff/chainPreNet/chainPreNet.c:88-137
  */
 #ifndef GACHAIN_H
 #define GACHAIN_H
@@ -60,8 +62,9 @@ extern "C" {
  * 2 = gac_axt_cut and the clip-aware gac_axt_*_clip entry points (netToAxt).
  * 3 = gac_chain_psl_counts[_device] (chainToPsl).
  * 4 = gac_net_write_ex and gac_net_release (chainNet frees a net under its writers).
- * 5 = gac_depth_count and gac_depth_count_host (netSyntenic). */
-#define GAC_ABI_MINOR 5
+ * 5 = gac_depth_count and gac_depth_count_host (netSyntenic).
+ * 6 = gac_prenet_keep and gac_prenet_keep_host (chainPreNet). */
+#define GAC_ABI_MINOR 6
 
 /* return codes */
 #define GAC_OK 0
@@ -356,6 +359,65 @@ int gac_depth_count(gac_ctx *ctx, int64_t n, const int32_t *seq, const int32_t *
  * one sweep (netSyntenic -host). */
 int gac_depth_count_host(int64_t n, const int32_t *seq, const int32_t *start, const int32_t *end,
                          const int8_t *delta, int32_t threshold, int32_t *count);
+
+/* ---- chains worth netting (chainPreNet) -------------------------------------
+ * keep[i] = 1 when chain i would be written by chainPreNet
+ * (kent/src/hg/mouseStuff/chainPreNet/chainPreNet.c:104-137): in the order
+ * given (the file's, best score first) a chain is kept when some base of one
+ * of its blocks, on the target or on the query side, lies outside the blocks
+ * of every chain kept before it, those blocks widened by `pad` bases at both
+ * ends and cut to [0, size of the sequence).  A dropped chain covers nothing.
+ * Chain i has the blocks [blk_off[i], blk_off[i + 1]) (blk_off[0] = 0,
+ * blk_off[n] = n_blocks): block b covers [blk_t[b], blk_t[b] + blk_size[b])
+ * of target sequence t_seq[i] and [blk_q[b], blk_q[b] + blk_size[b]) of query
+ * sequence q_seq[i]; the query coordinates are taken as they stand in the
+ * chain file, for '-' chains too, as the reference takes them.  Target and
+ * query sequences are numbered apart (t_sizes[n_tseq], q_sizes[n_qseq]).  A
+ * chain with t_seq or q_seq -1 is skipped (a haplotype query without
+ * -inclHap): it gets 0 and covers nothing.  A block of size 0 has no base of
+ * its own but covers its pad, as there.
+ *
+ * The device works in rounds of two passes: every pass
+ * writes, per base, the lowest rank among the chains that cover it, and asks
+ * every undecided chain for a base that nothing before it covers.  The per-base
+ * words take 4 bytes a base of the largest sequence group: the sequences that
+ * some counted chain names, of one side at a time, grouped to fit
+ * GAC_PRENET_FC_BYTES (default: three quarters of the device memory free at
+ * the call, after the call's other buffers).  A sequence larger than that, or
+ * max_rounds rounds (<= 0: GAC_PRENET_MAX_ROUNDS) without a decision for every
+ * chain, hands the whole call to gac_prenet_keep_host; stats says so.
+ *
+ * GAC_E_ARG: a negative start or size, a block past the end of its sequence,
+ * a sequence number outside its table, pad < 0, offsets that do not ascend, or
+ * more than GAC_PRENET_MAX_ITEMS chains or blocks (what the reference does
+ * with such input is undefined: it writes outside its bitmap).  n == 0 returns
+ * GAC_OK without a launch.  Exact integers.  Host buffers, synchronous; needs
+ * neither genomes nor a scoring setup.  stats may be NULL. */
+#define GAC_PRENET_MAX_ROUNDS 32
+#define GAC_PRENET_MAX_ITEMS 2147483645
+#define GAC_PRENET_ON_DEVICE 0   /* gac_prenet_stats.fell_back */
+#define GAC_PRENET_FELL_ROUNDS 1 /* max_rounds reached: finished on the host */
+#define GAC_PRENET_FELL_MEMORY 2 /* a sequence larger than the budget: host */
+typedef struct gac_prenet_stats {
+    int32_t rounds;    /* rounds run on the device */
+    int32_t passes;    /* mark + check passes over all groups (two a round) */
+    int32_t groups[2]; /* sequence groups of the target / query side */
+    int32_t fell_back; /* GAC_PRENET_ON_DEVICE or why the host finished */
+    int32_t pad_;
+    int64_t kept;      /* chains with keep 1 */
+} gac_prenet_stats;
+int gac_prenet_keep(gac_ctx *ctx, int64_t n, const int64_t *blk_off, const int32_t *t_seq,
+                    const int32_t *q_seq, int64_t n_blocks, const int32_t *blk_t,
+                    const int32_t *blk_q, const int32_t *blk_size, int32_t n_tseq,
+                    const int32_t *t_sizes, int32_t n_qseq, const int32_t *q_sizes, int32_t pad,
+                    int32_t max_rounds, uint8_t *keep, gac_prenet_stats *stats);
+/* The reference's own pass, chain by chain over one bitmap per named sequence
+ * and side; no device (chainPreNet -host, the fallbacks). */
+int gac_prenet_keep_host(int64_t n, const int64_t *blk_off, const int32_t *t_seq,
+                         const int32_t *q_seq, int64_t n_blocks, const int32_t *blk_t,
+                         const int32_t *blk_q, const int32_t *blk_size, int32_t n_tseq,
+                         const int32_t *t_sizes, int32_t n_qseq, const int32_t *q_sizes,
+                         int32_t pad, uint8_t *keep, gac_prenet_stats *stats);
 
 /* ---- alignment text (chainToAxt) ------------------------------------------
  * A piece is a window of consecutive blocks of one chain (gac_window: chain,
@@ -819,7 +881,8 @@ int gac_synchronize(gac_ctx *ctx);
 #define GAC_K_TILE 1     /* tile scoring: bases, gaps, per-tile scan (dominant) */
 #define GAC_K_COMBINE 2  /* multi-tile range combine */
 #define GAC_K_DEPTH 3    /* gac_depth_count: events, sort, scans, counts (one lap per call) */
-#define GAC_K_COUNT 4
+#define GAC_K_PRENET 4   /* gac_prenet_keep: every pass's fill, scans, mark and check (one lap per call) */
+#define GAC_K_COUNT 5
 #define GAC_PROF_ALL ((1 << GAC_K_COUNT) - 1)
 /* Event timing of each launch of the kernels in `mask` (bits 1 << GAC_K_*;
  * 0 = off, GAC_PROF_ALL = all).  Each timed kernel adds two event markers
