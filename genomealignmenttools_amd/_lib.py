@@ -145,6 +145,12 @@ _PROTOS = {
     "gac_genome_seq_name": (C.c_char_p, [C.c_void_p, C.c_int, C.c_int32]),
     "gac_genome_decode": (
         C.c_int, [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_char_p]),
+    "gac_genome_planes": (
+        C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                  C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    "gac_genome_load_2bit_runs": (
+        C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p]),
     "gac_genome_want_softmask": (C.c_int, [C.c_void_p, C.c_int]),
     "gac_genome_add_seq_masked": (
         C.c_int,

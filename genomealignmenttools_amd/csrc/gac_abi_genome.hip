@@ -39,10 +39,17 @@ static int add_seq(gac_ctx *c, int side, const char *name, int32_t size, const u
                    const int32_t *m_sizes = nullptr) {
     Genome *g = side_of(c, side);
     if (!g || !name || size < 0 || (size > 0 && !packed) || n_nblocks < 0 || n_mask < 0 ||
+        (n_nblocks > 0 && (!n_starts || !n_sizes)) ||
         (n_mask > 0 && (!m_starts || !m_sizes)))
         return gac_fail(GAC_E_ARG, "gac_genome_add_seq: bad argument");
     if (g->final) return gac_fail(GAC_E_STATE, "genome side %d already finalized", side);
     if (g->index.count(name)) return gac_fail(GAC_E_ARG, "duplicate sequence %s", name);
+    // (before anything is stored: a refused call leaves the side as it was)
+    for (int32_t i = 0; i < n_nblocks; ++i) {
+        const int64_t s = n_starts[i], len = n_sizes[i];
+        if (s < 0 || len < 0 || s + len > size)
+            return gac_fail(GAC_E_FORMAT, "N block %d of %s out of range", i, name);
+    }
     int32_t idx = (int32_t)g->names.size();
     g->index[name] = idx;
     g->names.push_back(name);
@@ -78,8 +85,6 @@ static int add_seq(gac_ctx *c, int side, const char *name, int32_t size, const u
     }
     for (int32_t i = 0; i < n_nblocks; ++i) {
         int64_t s = n_starts[i], len = n_sizes[i];
-        if (s < 0 || len < 0 || s + len > size)
-            return gac_fail(GAC_E_FORMAT, "N block %d of %s out of range", i, name);
         while (len > 0) {
             int32_t piece = (int32_t)(len < 1024 ? len : 1024);
             g->npieces.push_back(NPiece{s, piece, 0});
@@ -498,6 +503,18 @@ extern "C" int gac_genome_load_2bit(gac_ctx *c, int side, const char *path) {
     return gac_genome_load_twobit(c, side, &tb);
 }
 
+extern "C" int gac_genome_load_2bit_runs(gac_ctx *c, int side, const char *path,
+                                         const uint8_t *keep, const int64_t *run_off,
+                                         const int32_t *run_lo, const int32_t *run_hi) {
+    gac_clear_error();
+    if (!side_of(c, side) || !path || (run_off && (!run_lo || !run_hi)))
+        return gac_fail(GAC_E_ARG, "gac_genome_load_2bit_runs: bad argument");
+    gac_twobit tb;
+    int rc = gac_twobit_open(path, &tb);
+    if (rc != GAC_OK) return rc;
+    return gac_genome_load_twobit_runs(c, side, &tb, keep, run_off, run_lo, run_hi);
+}
+
 extern "C" int gac_genome_load_twobit(gac_ctx *c, int side, gac_twobit *tbp) {
     return gac_genome_load_twobit_runs(c, side, tbp, nullptr, nullptr, nullptr, nullptr);
 }
@@ -618,6 +635,22 @@ extern "C" int gac_genome_decode(gac_ctx *c, int side, int32_t i, int32_t start,
             out[p - start] = nt[code];
         }
     }
+    return GAC_OK;
+}
+
+extern "C" int gac_genome_planes(gac_ctx *c, int side, const void **planes,
+                                 const uint32_t **nmask, const uint32_t **lmask,
+                                 int64_t *n_words) {
+    gac_clear_error();
+    Genome *g = side_of(c, side);
+    if (!g || !planes || !nmask || !lmask || !n_words)
+        return gac_fail(GAC_E_ARG, "gac_genome_planes: bad argument");
+    CTX_LOCK(c);
+    if (!g->final) return gac_fail(GAC_E_STATE, "genome side %d is not finalized", side);
+    *planes = g->planes;
+    *nmask = g->nmask;
+    *lmask = g->lmask;
+    *n_words = g->n_words;
     return GAC_OK;
 }
 

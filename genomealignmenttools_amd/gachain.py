@@ -140,12 +140,52 @@ class Engine:
         self._gap = gap
 
     # ---- genomes
-    def load_2bit(self, side: int, path: str, soft_mask: bool = False) -> None:
+    def load_2bit(self, side: int, path: str, soft_mask: bool = False, keep=None,
+                  runs=None) -> None:
         """soft_mask: also keep the file's mask runs as the soft-mask plane
-        (chain_composition, decode_case); off, the load is unchanged."""
+        (chain_composition, decode_case); off, the load is unchanged.
+        keep: one flag per sequence of the file, false = not loaded.
+        runs: the sparse upload (gac_genome_load_2bit_runs) -- per sequence of
+        the file a list of (lo, hi) word runs, 32 bases per word; only these
+        words of the planes are uploaded."""
         if soft_mask:
             check(lib().gac_genome_want_softmask(self.h, side))
-        check(lib().gac_genome_load_2bit(self.h, side, path.encode()))
+        if keep is None and runs is None:
+            check(lib().gac_genome_load_2bit(self.h, side, path.encode()))
+            return
+        k = None if keep is None else np.ascontiguousarray(np.asarray(keep, bool), np.uint8)
+        off = lo = hi = None
+        if runs is not None:
+            off = np.zeros(len(runs) + 1, np.int64)
+            off[1:] = np.cumsum([len(r) for r in runs])
+            flat = np.asarray([x for r in runs for x in r], np.int64).reshape(-1, 2)
+            flat = np.concatenate([flat, np.zeros((1, 2), np.int64)])  # (never NULL)
+            lo = np.ascontiguousarray(flat[:, 0], np.int32)
+            hi = np.ascontiguousarray(flat[:, 1], np.int32)
+        check(lib().gac_genome_load_2bit_runs(
+            self.h, side, path.encode(), _p(k) if k is not None else None,
+            _p(off) if off is not None else None, _p(lo) if lo is not None else None,
+            _p(hi) if hi is not None else None))
+
+    def genome_planes(self, side: int):
+        """The resident arrays of a finalized side copied back
+        (gac_genome_planes): (planes uint32 [n + 4, 2] {bit-0, bit-1 plane},
+        nmask uint32 [n + 4], lmask uint32 [n + 4] or None), n the side's word
+        count; the four trailing words are the padding scoring windows read."""
+        pl, nm, lm = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        n = C.c_int64()
+        check(lib().gac_genome_planes(self.h, side, C.byref(pl), C.byref(nm), C.byref(lm),
+                                      C.byref(n)))
+        m = n.value + 4
+        planes = np.zeros((m, 2), np.uint32)
+        nmask = np.zeros(m, np.uint32)
+        self.d2h(planes, pl.value)
+        self.d2h(nmask, nm.value)
+        lmask = None
+        if lm.value:
+            lmask = np.zeros(m, np.uint32)
+            self.d2h(lmask, lm.value)
+        return planes, nmask, lmask
 
     def add_sequences(self, side: int, seqs: Iterable, mask_runs=None) -> None:
         """seqs: iterable of (name, size, packed uint8 .2bit payload, n_starts, n_sizes).

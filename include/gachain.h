@@ -190,6 +190,24 @@ const char *gac_genome_seq_name(gac_ctx *ctx, int side, int32_t index);
  * proves the resident layout round-trips; out must hold end-start bytes). */
 int gac_genome_decode(gac_ctx *ctx, int side, int32_t index, int32_t start,
                       int32_t end, char *out);
+/* The resident arrays of a finalized side (read-only; test aid): device
+ * pointers of planes (uint2 {bit-0 plane, bit-1 plane} per 32-base word),
+ * nmask and lmask (NULL without the soft-mask plane), and the word count.
+ * Each array holds n_words + 4 words: the four past the sequences are
+ * planes 0, nmask 0xffffffff, lmask 0 (scoring windows read word w + 1).
+ * GAC_E_ARG: bad side or NULL pointer; GAC_E_STATE: side not finalized. */
+int gac_genome_planes(gac_ctx *ctx, int side, const void **planes, const uint32_t **nmask,
+                      const uint32_t **lmask, int64_t *n_words);
+/* gac_genome_load_2bit with the loader's two filters.  keep (may be NULL):
+ * one byte per sequence of the file, 0 = not loaded.  run_off (may be NULL):
+ * the sparse upload -- sequence i of the file (kept or not) is uploaded only
+ * in its word runs [run_lo[r], run_hi[r]) (32-base words, clipped to the
+ * sequence), r in [run_off[i], run_off[i + 1]); N runs are applied to every
+ * word, plane words outside the runs are unspecified.  The sparse upload does
+ * not carry the soft-mask plane (GAC_E_ARG). */
+int gac_genome_load_2bit_runs(gac_ctx *ctx, int side, const char *path, const uint8_t *keep,
+                              const int64_t *run_off, const int32_t *run_lo,
+                              const int32_t *run_hi);
 
 /* ---- soft-mask plane (opt-in; chainAntiRepeat) ---------------------------
  * The reference reads sequence with twoBitReadSeqFragExt(doMask=TRUE)
