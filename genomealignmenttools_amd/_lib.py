@@ -25,9 +25,10 @@ GAC_OK = 0
 GAC_T = 0
 GAC_Q = 1
 GAC_WANT_LOCAL = 1
-GAC_K_PLAN, GAC_K_TILE, GAC_K_COMBINE, GAC_K_DEPTH, GAC_K_PRENET = 0, 1, 2, 3, 4
+GAC_K_PLAN, GAC_K_TILE, GAC_K_COMBINE, GAC_K_DEPTH, GAC_K_PRENET, GAC_K_AXTFILTER = 0, 1, 2, 3, 4, 5
 GAC_PRENET_MAX_ROUNDS = 32
 GAC_PRENET_ON_DEVICE, GAC_PRENET_FELL_ROUNDS, GAC_PRENET_FELL_MEMORY = 0, 1, 2
+GAC_AXTF_MAX_WINDOW = 1024
 
 _lock = threading.Lock()
 _lib = None
@@ -116,6 +117,11 @@ class PrenetStats(C.Structure):
                 ("fell_back", C.c_int32), ("pad_", C.c_int32), ("kept", C.c_int64)]
 
 
+class AxtFilterStats(C.Structure):
+    _fields_ = [("kept", C.c_int64), ("windows", C.c_int64), ("host_entries", C.c_int64),
+                ("batches", C.c_int32), ("fell_back", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "gac_abi_version": (C.c_int, []),
@@ -182,6 +188,12 @@ _PROTOS = {
         C.c_int, [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                   C.c_void_p]),
+    "gac_axt_filter": (
+        C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gac_axt_filter_host": (
+        C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                  C.c_double, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]),
     "gac_antirepeat_pass": (
         C.c_int, [C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int]),
     "gac_abi_minor": (C.c_int, []),

@@ -1,7 +1,7 @@
 // gac_kernels.h -- device data layout shared by the HIP kernels and the
 // C-ABI implementation (gac_device.hip and the gac_abi_*.hip units), and the one declaration of
-// every launcher of gac_kernels.hip, gac_compose.hip, gac_axtout.hip, gac_depth.hip and
-// gac_prenet.hip (each includes this header, so its definitions are checked against it).
+// every launcher of gac_kernels.hip, gac_compose.hip, gac_axtout.hip, gac_depth.hip,
+// gac_prenet.hip and gac_axtfilter.hip (each includes this header, so its definitions are checked against it).
 // gfx950 only.
 //
 // HBM layout (see DESIGN.md "Data layout in HBM"):
@@ -474,5 +474,33 @@ hipError_t launch_prenet_check(const PrenetArgs &a, hipStream_t s);
 // undecided chains that are not open are dropped, and the counts are added up
 hipError_t launch_prenet_decide(const PrenetArgs &a, int pass, hipStream_t s);
 hipError_t launch_prenet_flags(const PrenetArgs &a, uint8_t *keep, hipStream_t s);
+
+// ---- gac_axtfilter.hip: filterAxtIdentityEntropy's window test (gac_axt_filter).
+// The unit of work is a chunk: up to kAxtfTile - window consecutive window
+// starts of one entry, whose kAxtfTile - 1 columns at most are one workgroup's
+// tile.  ent[i].chunk0 = the first chunk of entry i (ent[n].chunk0 = all
+// chunks; an entry shorter than the window has none).
+constexpr int kAxtfTile = 2048;       // columns of a tile, one less used: the packed prefix
+                                      // counts are 11-bit fields (<= 2047)
+constexpr int kAxtfMaxWindow = 1024;  // GAC_AXTF_MAX_WINDOW: a chunk keeps >= 1024 starts
+struct AxtfEntry {
+    int64_t t, q;    // byte offsets of the rows in text
+    int32_t len;     // columns
+    int32_t pad;
+    int64_t chunk0;
+};
+static_assert(sizeof(AxtfEntry) == 32, "AxtfEntry layout");
+struct AxtfArgs {
+    const uint8_t *text;
+    int64_t text_bytes;
+    const AxtfEntry *ent;  // [n + 1]
+    int64_t n;
+    int32_t window, m_min;  // a window passes the identity test with >= m_min matches
+    const double *term;     // [window (window + 1) / 2] p log p at n (n - 1) / 2 + k - 1
+    double ln2, min_entropy;
+    uint32_t *keep;  // [n] one word an entry (zeroed by the caller): passing chunks store 1
+};
+// enforces 1 <= window <= kAxtfMaxWindow (the tile bound) and the grid limit
+hipError_t launch_axt_filter(const AxtfArgs &a, int64_t chunks, hipStream_t s);
 
 }  // namespace gac

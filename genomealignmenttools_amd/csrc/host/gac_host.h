@@ -156,6 +156,16 @@ int gac_prenet_check(int64_t n, const int64_t *blk_off, const int32_t *t_seq, co
                      const int32_t *blk_size, int32_t n_tseq, const int32_t *t_sizes,
                      int32_t n_qseq, const int32_t *q_sizes, int32_t pad, const uint8_t *keep);
 
+/* gac_axt_filter's argument check and its two host-made tables (shared with
+ * gac_axt_filter_host): the smallest match count of a window that reaches
+ * min_ident (window + 1: none), and the entropy terms p * log(p), p = k / n,
+ * at [n (n - 1) / 2 + k - 1] for 1 <= k <= n <= window (malloc'ed; NULL: out
+ * of memory) */
+int gac_axtf_check(int64_t n, const char *text, int64_t text_bytes, const int64_t *t_off,
+                   const int64_t *q_off, const int32_t *len, int32_t window, const uint8_t *keep);
+int32_t gac_axtf_mmin(double min_ident, int32_t window);
+double *gac_axtf_terms(int32_t window);
+
 /* ---- host view of a resident sequence (kept after gac_genome_finalize) ----
  * packed: 2 bits/base MSB-first (T=0 C=1 A=2 G=3); N runs merged and sorted. */
 typedef struct gac_seq_view {

@@ -17,6 +17,8 @@ netSyntenic's dupeTree (netSyntenic.c:63)    Engine.depth_count(seq, start, end,
                                              depth_count_host(...): the same on the CPU
 chainPreNet's chainUsed (chainPreNet.c:104)  Engine.prenet_keep(blk_off, t_seq, q_seq, ...)
                                              prenet_keep_host(...): the reference's own pass
+filterAxtIdentityEntropy.py's checkAxt (:88) Engine.axt_filter(t_rows, q_rows, ident, entropy, W)
+                                             axt_filter_host(...): the same on host threads
 axtScoreUngapped per block (axt.c:186-194)   Engine.score_blocks / score_text_blocks (caller text)
 cBlockFindCrossover (chainConnect.c:61-105)  Engine.crossovers / text_crossovers (caller text)
 chainBlocks' kd-tree DP (chainBlock.c:400)   Engine.chain_dp_blocks (total, predecessor per block)
@@ -269,6 +271,21 @@ class Engine:
                                     _p(a[3]), _p(a[4]), _p(a[5]), len(a[6]), _p(a[6]), len(a[7]),
                                     _p(a[7]), int(pad), int(max_rounds), _p(keep), C.byref(st)))
         return keep, _prenet_stats(st)
+
+    # ---- alignments worth chaining (filterAxtIdentityEntropy.py)
+    def axt_filter(self, t_rows, q_rows, min_ident: float, min_entropy: float, window: int):
+        """Which alignments filterAxtIdentityEntropy.py writes (gac_axt_filter):
+        t_rows and q_rows are the target and query rows of the entries (bytes
+        or str; a target row may be longer than its query row, whose length
+        counts).  Returns (keep uint8 [n], stats): kept, windows,
+        host_entries, batches, fell_back."""
+        text, t_off, q_off, ln = _axt_filter_args(t_rows, q_rows)
+        keep = np.zeros(len(ln), np.uint8)
+        st = _lib.AxtFilterStats()
+        check(lib().gac_axt_filter(self.h, len(ln), text, len(text), _p(t_off), _p(q_off), _p(ln),
+                                   float(min_ident), float(min_entropy), int(window), _p(keep),
+                                   C.byref(st)))
+        return keep, _axt_filter_stats(st)
 
     # ---- alignment text (chainToAxt)
     @staticmethod
@@ -666,6 +683,41 @@ def prenet_keep_host(blk_off, t_seq, q_seq, blk_t, blk_q, blk_size, t_sizes, q_s
     return keep, _prenet_stats(st)
 
 
+def _axt_filter_args(t_rows, q_rows):
+    rows = [[r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in side]
+            for side in (t_rows, q_rows)]
+    if len(rows[0]) != len(rows[1]):
+        raise ValueError("axt_filter: as many target rows as query rows")
+    n = len(rows[0])
+    ln = np.fromiter((len(q) for q in rows[1]), np.int32, n)
+    tl = np.fromiter((len(t) for t in rows[0]), np.int64, n)
+    if np.any(tl < ln):
+        raise ValueError("axt_filter: a target row shorter than its query row")
+    # t0 q0 t1 q1 ...: the query row of entry i follows its whole target row
+    sizes = np.stack([tl, ln.astype(np.int64)], axis=1).ravel()
+    starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    text = b"".join(x for pair in zip(rows[0], rows[1]) for x in pair)
+    return text, np.ascontiguousarray(starts[0:2 * n:2]), np.ascontiguousarray(starts[1:2 * n:2]), ln
+
+
+def _axt_filter_stats(st) -> dict:
+    return dict(kept=st.kept, windows=st.windows, host_entries=st.host_entries, batches=st.batches,
+                fell_back=st.fell_back)
+
+
+def axt_filter_host(t_rows, q_rows, min_ident: float, min_entropy: float, window: int,
+                    nthreads: int = 0):
+    """Engine.axt_filter's result with running window counts on host threads
+    (gac_axt_filter_host; no device): (keep uint8 [n], stats)."""
+    text, t_off, q_off, ln = _axt_filter_args(t_rows, q_rows)
+    keep = np.zeros(len(ln), np.uint8)
+    st = _lib.AxtFilterStats()
+    check(lib().gac_axt_filter_host(len(ln), text, len(text), _p(t_off), _p(q_off), _p(ln),
+                                    float(min_ident), float(min_entropy), int(window), int(nthreads),
+                                    _p(keep), C.byref(st)))
+    return keep, _axt_filter_stats(st)
+
+
 def antirepeat_pass(score: float, match, rep: int, total: int, min_score: int = 5000) -> bool:
     """chainAntiRepeat's keep/drop decision for one chain from its composition
     (gac_antirepeat_pass: degeneracyFilter then repeatFilter; host only)."""
@@ -686,4 +738,5 @@ def twobit_mask_runs(path: str, name: str) -> Tuple[np.ndarray, np.ndarray]:
 
 
 __all__ = ["Engine", "ChainSet", "GapCosts", "read_score_scheme", "GAC_T", "GAC_Q",
-           "antirepeat_pass", "twobit_mask_runs", "depth_count_host", "prenet_keep_host"]
+           "antirepeat_pass", "twobit_mask_runs", "depth_count_host", "prenet_keep_host",
+           "axt_filter_host"]

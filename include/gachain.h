@@ -43,6 +43,8 @@
  *                          (writeChainPart, kent/src/hg/mouseStuff/netToAxt/netToAxt.c:76-105)
  *   gac_prenet_keep       <- chainUsed + setWithPad
  *                                                 kent/src/hg/mouseStuff/chainPreNet/chainPreNet.c:88-137
+ *   gac_axt_filter        <- getSeqIdent + getEntropy + checkAxt + processHit's counts
+ *                                                 src/filterAxtIdentityEntropy.py:32-69,88-110,144-162
  */
 #ifndef GACHAIN_H
 #define GACHAIN_H
@@ -63,8 +65,9 @@ extern "C" {
  * 3 = gac_chain_psl_counts[_device] (chainToPsl).
  * 4 = gac_net_write_ex and gac_net_release (chainNet frees a net under its writers).
  * 5 = gac_depth_count and gac_depth_count_host (netSyntenic).
- * 6 = gac_prenet_keep and gac_prenet_keep_host (chainPreNet). */
-#define GAC_ABI_MINOR 6
+ * 6 = gac_prenet_keep and gac_prenet_keep_host (chainPreNet).
+ * 7 = gac_axt_filter and gac_axt_filter_host (filterAxtIdentityEntropy.py). */
+#define GAC_ABI_MINOR 7
 
 /* return codes */
 #define GAC_OK 0
@@ -436,6 +439,54 @@ int gac_prenet_keep_host(int64_t n, const int64_t *blk_off, const int32_t *t_seq
                          const int32_t *blk_q, const int32_t *blk_size, int32_t n_tseq,
                          const int32_t *t_sizes, int32_t n_qseq, const int32_t *q_sizes,
                          int32_t pad, uint8_t *keep, gac_prenet_stats *stats);
+
+/* ---- alignments worth chaining (filterAxtIdentityEntropy.py) --------------
+ * keep[i] = 1 iff alignment i has a window of `window` columns that passes
+ * the script's identity and entropy test (src/filterAxtIdentityEntropy.py:
+ * checkAxt :88-110 over processHit's counts :144-162, getSeqIdent :41-42,
+ * getEntropy :45-69).  Entry i is two rows of len[i] columns of alignment
+ * text at text + t_off[i] (target) and text + q_off[i] (query); rows may lie
+ * anywhere in `text` and may overlap.  With both characters ASCII-lowercased a
+ * column is a match when they are equal ('n'/'n' and '-'/'-' match), and the
+ * target adds to one of four counts when it is a, c, g or t.  The entry is
+ * kept iff some start s with target[s] != '-' and s + window <= len has, over
+ * [s, s + window), 100.0 * matches / window >= min_ident and H >= min_entropy;
+ * H = 0.0 without a counted base, else with p = k / n over the counts k in the
+ * order a, c, g, t, zero counts skipped: e = 0.0; e -= p * log(p); H = e /
+ * log(2), all in doubles.  The order of the terms is part of the result.
+ *
+ * Exact by construction: the host makes, with libm, the smallest match count
+ * that reaches min_ident and the table of the terms p * log(p); the device
+ * (and the host twin) compare integers, subtract table entries in that order
+ * and divide once.  The device takes windows up to
+ * GAC_AXTF_MAX_WINDOW; a larger one runs the host twin for every entry
+ * (fell_back 1).  The entries go in batches whose text stays under
+ * GAC_AXTF_BATCH_BYTES (an environment knob; default: a quarter of the free
+ * device memory, at most 256 MiB); an entry alone over that is decided by the
+ * host twin (fell_back 2).
+ *
+ * GAC_E_ARG: window < 1, n < 0, a negative length or offset, a row reaching
+ * past text_bytes, a NULL array with n > 0.  n == 0 returns GAC_OK without a
+ * launch.  Host buffers, synchronous; needs neither genomes nor a scoring
+ * setup.  st may be NULL. */
+#define GAC_AXTF_MAX_WINDOW 1024
+typedef struct gac_axtfilter_stats {
+    int64_t kept, windows;      /* entries kept; window starts examined */
+    int64_t host_entries;       /* entries decided by the host twin */
+    int32_t batches, fell_back; /* 0 device; 1 window over the device cap (all entries on the host);
+                                   2 some entry over the byte budget (those entries on the host) */
+} gac_axtfilter_stats;
+int gac_axt_filter(gac_ctx *ctx, int64_t n, const char *text, int64_t text_bytes,
+                   const int64_t *t_off, const int64_t *q_off, const int32_t *len,
+                   double min_ident, double min_entropy, int32_t window,
+                   uint8_t *keep, gac_axtfilter_stats *st);
+/* The same decision with running window counts on nthreads host threads (<= 0:
+ * GAC_THREADS, else all CPUs); no device (filterAxtIdentityEntropy.py -host,
+ * the fallbacks). */
+int gac_axt_filter_host(int64_t n, const char *text, int64_t text_bytes,
+                        const int64_t *t_off, const int64_t *q_off, const int32_t *len,
+                        double min_ident, double min_entropy, int32_t window, int nthreads,
+                        uint8_t *keep, gac_axtfilter_stats *st);
 
 /* ---- alignment text (chainToAxt) ------------------------------------------
  * A piece is a window of consecutive blocks of one chain (gac_window: chain,
@@ -900,7 +951,8 @@ int gac_synchronize(gac_ctx *ctx);
 #define GAC_K_COMBINE 2  /* multi-tile range combine */
 #define GAC_K_DEPTH 3    /* gac_depth_count: events, sort, scans, counts (one lap per call) */
 #define GAC_K_PRENET 4   /* gac_prenet_keep: every pass's fill, scans, mark and check (one lap per call) */
-#define GAC_K_COUNT 5
+#define GAC_K_AXTFILTER 5 /* gac_axt_filter: the window kernel (one lap per batch) */
+#define GAC_K_COUNT 6
 #define GAC_PROF_ALL ((1 << GAC_K_COUNT) - 1)
 /* Event timing of each launch of the kernels in `mask` (bits 1 << GAC_K_*;
  * 0 = off, GAC_PROF_ALL = all).  Each timed kernel adds two event markers
