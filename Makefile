@@ -23,9 +23,9 @@ HOST_SRC := $(wildcard $(CSRC)/host/*.c)
 HOST_OBJ := $(patsubst $(CSRC)/host/%.c,$(OBJDIR)/host/%.o,$(HOST_SRC))
 # kernels and their launchers, then the C ABI by subject (gac_device.hip:
 # scoring; gac_abi_*.hip; all over gac_ctx.h), then the rank communicator
-HIP_SRC  := $(CSRC)/gac_kernels.hip $(CSRC)/gac_compose.hip $(CSRC)/gac_axtout.hip $(CSRC)/gac_depth.hip $(CSRC)/gac_prenet.hip $(CSRC)/gac_axtfilter.hip $(CSRC)/gac_dp.hip $(CSRC)/gac_dptree.hip \
+HIP_SRC  := $(CSRC)/gac_kernels.hip $(CSRC)/gac_compose.hip $(CSRC)/gac_axtout.hip $(CSRC)/gac_depth.hip $(CSRC)/gac_prenet.hip $(CSRC)/gac_axtfilter.hip $(CSRC)/gac_axtpsl.hip $(CSRC)/gac_dp.hip $(CSRC)/gac_dptree.hip \
             $(CSRC)/gac_abi_context.hip $(CSRC)/gac_abi_genome.hip $(CSRC)/gac_abi_chains.hip $(CSRC)/gac_device.hip \
-            $(CSRC)/gac_abi_dp.hip $(CSRC)/gac_abi_seqout.hip $(CSRC)/gac_abi_depth.hip $(CSRC)/gac_abi_prenet.hip $(CSRC)/gac_abi_axtfilter.hip $(CSRC)/gac_comm.hip
+            $(CSRC)/gac_abi_dp.hip $(CSRC)/gac_abi_seqout.hip $(CSRC)/gac_abi_depth.hip $(CSRC)/gac_abi_prenet.hip $(CSRC)/gac_abi_axtfilter.hip $(CSRC)/gac_abi_axtpsl.hip $(CSRC)/gac_comm.hip
 HIP_OBJ  := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 HDRS     := include/gachain.h $(CSRC)/gac_kernels.h $(CSRC)/gac_dp.h $(CSRC)/gac_ctx.h $(wildcard $(CSRC)/host/*.h)
 
@@ -38,7 +38,7 @@ EXECDIR  := $(PKG)/libexec
 # before anything touches the GPU.  Either can be overridden from outside.
 # NetFilterNonNested.perl, chainSort, chainMergeSort and chainToPslBasic are
 # host-only: in bin/.
-GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt netToAxt chainToPsl netSyntenic chainPreNet filterAxtIdentityEntropy.py
+GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt netToAxt chainToPsl netSyntenic chainPreNet filterAxtIdentityEntropy.py axtToPsl
 HOST_TOOLS := NetFilterNonNested.perl chainSort chainMergeSort chainToPslBasic
 TOOLS    := $(addprefix $(EXECDIR)/,$(GPU_TOOLS)) $(addprefix $(BINDIR)/,$(GPU_TOOLS)) \
             $(addprefix $(BINDIR)/,$(HOST_TOOLS))

@@ -26,9 +26,11 @@ GAC_T = 0
 GAC_Q = 1
 GAC_WANT_LOCAL = 1
 GAC_K_PLAN, GAC_K_TILE, GAC_K_COMBINE, GAC_K_DEPTH, GAC_K_PRENET, GAC_K_AXTFILTER = 0, 1, 2, 3, 4, 5
+GAC_K_AXTPSL = 6
 GAC_PRENET_MAX_ROUNDS = 32
 GAC_PRENET_ON_DEVICE, GAC_PRENET_FELL_ROUNDS, GAC_PRENET_FELL_MEMORY = 0, 1, 2
 GAC_AXTF_MAX_WINDOW = 1024
+GAC_AXTPSL_TILE = 512
 
 _lock = threading.Lock()
 _lib = None
@@ -122,6 +124,23 @@ class AxtFilterStats(C.Structure):
                 ("batches", C.c_int32), ("fell_back", C.c_int32)]
 
 
+class AxtPslEntry(C.Structure):
+    _fields_ = [("match", C.c_uint32), ("mis_match", C.c_uint32), ("rep_match", C.c_uint32),
+                ("n_count", C.c_uint32), ("q_num_insert", C.c_uint32), ("q_base_insert", C.c_uint32),
+                ("t_num_insert", C.c_uint32), ("t_base_insert", C.c_uint32), ("q_head", C.c_int32),
+                ("t_head", C.c_int32), ("q_tail", C.c_int32), ("t_tail", C.c_int32), ("cols", C.c_int32),
+                ("n_blocks", C.c_int32), ("block0", C.c_int64)]
+
+
+class AxtPslResult(C.Structure):
+    _fields_ = [("n", C.c_int64), ("n_blocks", C.c_int64), ("entry", C.c_void_p), ("block", C.c_void_p)]
+
+
+class AxtPslStats(C.Structure):
+    _fields_ = [("blocks", C.c_int64), ("columns", C.c_int64), ("host_entries", C.c_int64),
+                ("batches", C.c_int32), ("fell_back", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "gac_abi_version": (C.c_int, []),
@@ -194,6 +213,13 @@ _PROTOS = {
     "gac_axt_filter_host": (
         C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
                   C.c_double, C.c_int32, C.c_int, C.c_void_p, C.c_void_p]),
+    "gac_axt_psl": (
+        C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.POINTER(C.POINTER(AxtPslResult)), C.c_void_p]),
+    "gac_axt_psl_host": (
+        C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                  C.POINTER(C.POINTER(AxtPslResult)), C.c_void_p]),
+    "gac_axtpsl_free": (None, [C.POINTER(AxtPslResult)]),
     "gac_antirepeat_pass": (
         C.c_int, [C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int]),
     "gac_abi_minor": (C.c_int, []),

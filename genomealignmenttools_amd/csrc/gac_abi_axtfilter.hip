@@ -18,41 +18,6 @@ using namespace gac;
 
 static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-namespace {
-
-constexpr int64_t kAxtfDefaultBudget = 256ll << 20;  // bytes of text a batch
-constexpr int64_t kAxtfBatchEntries = 1ll << 21;     // entries a batch (64 MB of records)
-constexpr int64_t kAxtfJoinGap = 64;                 // spans this close are uploaded as one
-
-// The text a batch needs: the span of its target rows and the span of its
-// query rows (one span when they overlap or nearly touch, as the rows of an
-// axt file do; two when a caller keeps the sides apart).
-struct Spans {
-    int64_t tlo = 0, thi = 0, qlo = 0, qhi = 0;
-    bool any = false;
-    void add(int64_t t, int64_t q, int64_t L) {
-        if (!any) {
-            tlo = t, thi = t + L, qlo = q, qhi = q + L, any = true;
-            return;
-        }
-        tlo = std::min(tlo, t), thi = std::max(thi, t + L);
-        qlo = std::min(qlo, q), qhi = std::max(qhi, q + L);
-    }
-    bool joined() const { return tlo <= qhi + kAxtfJoinGap && qlo <= thi + kAxtfJoinGap; }
-    int64_t bytes() const {
-        return joined() ? std::max(thi, qhi) - std::min(tlo, qlo) : (thi - tlo) + (qhi - qlo);
-    }
-};
-
-struct Batch {
-    int64_t first, end;  // entries [first, end) of the call (those shorter than the window and
-                         // those left to the host among them are not uploaded)
-    int64_t n;           // entries uploaded
-    Spans sp;
-};
-
-}  // namespace
-
 extern "C" int gac_axt_filter(gac_ctx *c, int64_t n, const char *text, int64_t text_bytes,
                               const int64_t *t_off, const int64_t *q_off, const int32_t *len,
                               double min_ident, double min_entropy, int32_t window, uint8_t *keep,
@@ -94,51 +59,19 @@ extern "C" int gac_axt_filter(gac_ctx *c, int64_t n, const char *text, int64_t t
     hipStream_t s = c->stream;
 
     int64_t budget = 0;
-    if (const char *v = getenv("GAC_AXTF_BATCH_BYTES")) budget = atoll(v);
-    if (budget <= 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        budget = std::max<int64_t>(1, std::min<int64_t>((int64_t)(free_b / 4), kAxtfDefaultBudget));
-    }
+    HIPCHK(axt_batch_budget("GAC_AXTF_BATCH_BYTES", &budget));
 
-    // the batches: consecutive entries while their text stays under the budget
-    std::vector<Batch> batches;
-    std::vector<int64_t> host_idx;  // entries alone over the budget
-    int64_t windows = 0, n_dev = 0, max_n = 0, max_bytes = 0;
-    {
-        Batch b{0, 0, 0, Spans()};
-        auto close = [&](int64_t end) {
-            b.end = end;
-            if (b.n > 0) {
-                batches.push_back(b);
-                n_dev += b.n;
-                max_n = std::max(max_n, b.n);
-                max_bytes = std::max(max_bytes, b.sp.bytes());
-            }
-            b = Batch{end, end, 0, Spans()};
-        };
-        for (int64_t i = 0; i < n; ++i) {
-            keep[i] = 0;
-            const int64_t L = len[i];
-            if (L < W) continue;  // no window: no chunk, never kept
-            windows += L - W + 1;
-            Spans one;
-            one.add(t_off[i], q_off[i], L);
-            if (one.bytes() > budget) {
-                host_idx.push_back(i);
-                continue;
-            }
-            Spans with = b.sp;
-            with.add(t_off[i], q_off[i], L);
-            if (b.n > 0 && (with.bytes() > budget || b.n >= kAxtfBatchEntries)) {
-                close(i);
-                with = one;
-            }
-            b.sp = with;
-            ++b.n;
-        }
-        close(n);
+    // the batches (gac_ctx.h); an entry shorter than the window has no chunk and is never kept
+    AxtPlan plan;
+    int64_t windows = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        keep[i] = 0;
+        if (len[i] >= W) windows += len[i] - W + 1;
     }
+    axt_plan_batches(n, t_off, q_off, len, budget, [&](int64_t i) { return len[i] < W; }, plan);
+    const std::vector<AxtBatch> &batches = plan.batches;
+    const std::vector<int64_t> &host_idx = plan.host_idx;
+    const int64_t n_dev = plan.n_dev, max_n = plan.max_n, max_bytes = plan.max_bytes;
     lap("batches");
 
     std::vector<uint32_t> flags((size_t)n_dev, 0u);
@@ -192,13 +125,10 @@ extern "C" int gac_axt_filter(gac_ctx *c, int64_t n, const char *text, int64_t t
         double up_s = 0, k_s = 0;
         int64_t up_bytes = 0, done = 0;
         size_t next_host = 0;
-        for (const Batch &b : batches) {
+        for (const AxtBatch &b : batches) {
             // where the spans go in the batch's buffer, and the records against that
-            const Spans &sp = b.sp;
-            const bool joined = sp.joined();
-            const int64_t lo = std::min(sp.tlo, sp.qlo);
-            const int64_t t_base = joined ? sp.tlo - lo : 0;
-            const int64_t q_base = joined ? sp.qlo - lo : sp.thi - sp.tlo;
+            const AxtSpans &sp = b.sp;
+            const int64_t t_base = sp.t_base(), q_base = sp.q_base();
             ent.clear();
             int64_t chunks = 0;
             for (int64_t i = b.first; i < b.end; ++i) {
@@ -218,13 +148,7 @@ extern "C" int gac_axt_filter(gac_ctx *c, int64_t n, const char *text, int64_t t
             a.keep = (uint32_t *)(d + o_keep) + done;
 
             const double t0 = timing ? wall_s() : 0;
-            if (joined) {
-                rc = upload_staged(c, d + o_text, text + lo, (size_t)sp.bytes());
-            } else {
-                rc = upload_staged(c, d + o_text, text + sp.tlo, (size_t)(sp.thi - sp.tlo));
-                if (rc == GAC_OK)
-                    rc = upload_staged(c, d + o_text + q_base, text + sp.qlo, (size_t)(sp.qhi - sp.qlo));
-            }
+            rc = axt_upload_spans(c, d + o_text, text, sp);
             if (rc == GAC_OK) rc = upload_staged(c, d + o_ent, ent.data(), ent.size() * sizeof(AxtfEntry));
             if (rc != GAC_OK) return fail_rc(rc);
             up_bytes += sp.bytes() + (int64_t)(ent.size() * sizeof(AxtfEntry));

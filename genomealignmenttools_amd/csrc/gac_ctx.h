@@ -4,8 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <time.h>
 
+#include <algorithm>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -246,6 +248,109 @@ void axt_release(gac_ctx *c);
 inline int acgt_of_code(int code) {
     static const int m[4] = {3, 1, 0, 2};
     return m[code];
+}
+
+// ---- the batches of the alignment-text calls (gac_axt_filter, gac_axt_psl):
+// consecutive entries -- two rows of len[i] bytes at t_off[i] and q_off[i] of
+// the caller's text -- while the text they need stays under a byte budget.
+constexpr int64_t kAxtDefaultBudget = 256ll << 20;  // bytes of text a batch
+constexpr int64_t kAxtBatchEntries = 1ll << 21;     // entries a batch (64 MB of records)
+constexpr int64_t kAxtJoinGap = 64;                 // spans this close are uploaded as one
+
+// The text a batch needs: the span of its target rows and the span of its
+// query rows (one span when they overlap or nearly touch, as the rows of an
+// axt file do; two when a caller keeps the sides apart).
+struct AxtSpans {
+    int64_t tlo = 0, thi = 0, qlo = 0, qhi = 0;
+    bool any = false;
+    void add(int64_t t, int64_t q, int64_t L) {
+        if (!any) {
+            tlo = t, thi = t + L, qlo = q, qhi = q + L, any = true;
+            return;
+        }
+        tlo = std::min(tlo, t), thi = std::max(thi, t + L);
+        qlo = std::min(qlo, q), qhi = std::max(qhi, q + L);
+    }
+    bool joined() const { return tlo <= qhi + kAxtJoinGap && qlo <= thi + kAxtJoinGap; }
+    int64_t bytes() const {
+        return joined() ? std::max(thi, qhi) - std::min(tlo, qlo) : (thi - tlo) + (qhi - qlo);
+    }
+    // where the spans go in the batch's buffer: the rows of an entry at t and q
+    // of the text are at t_base() + (t - tlo) and q_base() + (q - qlo)
+    int64_t lo() const { return std::min(tlo, qlo); }
+    int64_t t_base() const { return joined() ? tlo - lo() : 0; }
+    int64_t q_base() const { return joined() ? qlo - lo() : thi - tlo; }
+};
+
+struct AxtBatch {
+    int64_t first, end;  // entries [first, end) of the call (the skipped ones and those left
+                         // to the host among them are not uploaded)
+    int64_t n;           // entries uploaded
+    AxtSpans sp;
+};
+
+struct AxtPlan {
+    std::vector<AxtBatch> batches;
+    std::vector<int64_t> host_idx;  // entries alone over the budget, ascending
+    int64_t n_dev = 0, max_n = 0, max_bytes = 0;  // entries uploaded; the largest batch
+};
+
+// skip(i): entry i takes no part (it is neither uploaded nor left to the host)
+template <class Skip>
+inline void axt_plan_batches(int64_t n, const int64_t *t_off, const int64_t *q_off, const int32_t *len,
+                             int64_t budget, Skip skip, AxtPlan &P) {
+    AxtBatch b{0, 0, 0, AxtSpans()};
+    auto close = [&](int64_t end) {
+        b.end = end;
+        if (b.n > 0) {
+            P.batches.push_back(b);
+            P.n_dev += b.n;
+            P.max_n = std::max(P.max_n, b.n);
+            P.max_bytes = std::max(P.max_bytes, b.sp.bytes());
+        }
+        b = AxtBatch{end, end, 0, AxtSpans()};
+    };
+    for (int64_t i = 0; i < n; ++i) {
+        if (skip(i)) continue;
+        const int64_t L = len[i];
+        AxtSpans one;
+        one.add(t_off[i], q_off[i], L);
+        if (one.bytes() > budget) {
+            P.host_idx.push_back(i);
+            continue;
+        }
+        AxtSpans with = b.sp;
+        with.add(t_off[i], q_off[i], L);
+        if (b.n > 0 && (with.bytes() > budget || b.n >= kAxtBatchEntries)) {
+            close(i);
+            with = one;
+        }
+        b.sp = with;
+        ++b.n;
+    }
+    close(n);
+}
+
+// the byte budget: the environment knob `env`, else a quarter of the free
+// device memory, at most kAxtDefaultBudget
+inline hipError_t axt_batch_budget(const char *env, int64_t *budget) {
+    *budget = 0;
+    if (const char *v = getenv(env)) *budget = atoll(v);
+    if (*budget > 0) return hipSuccess;
+    size_t free_b = 0, total_b = 0;
+    const hipError_t e = hipMemGetInfo(&free_b, &total_b);
+    if (e != hipSuccess) return e;
+    *budget = std::max<int64_t>(1, std::min<int64_t>((int64_t)(free_b / 4), kAxtDefaultBudget));
+    return hipSuccess;
+}
+
+// a batch's text into its buffer, in one span or two
+inline int axt_upload_spans(gac_ctx *c, char *d_text, const char *text, const AxtSpans &sp) {
+    if (sp.joined()) return upload_staged(c, d_text, text + sp.lo(), (size_t)sp.bytes());
+    int rc = upload_staged(c, d_text, text + sp.tlo, (size_t)(sp.thi - sp.tlo));
+    if (rc == GAC_OK)
+        rc = upload_staged(c, d_text + sp.q_base(), text + sp.qlo, (size_t)(sp.qhi - sp.qlo));
+    return rc;
 }
 
 struct CtxLock {

@@ -1,7 +1,7 @@
 // gac_kernels.h -- device data layout shared by the HIP kernels and the
 // C-ABI implementation (gac_device.hip and the gac_abi_*.hip units), and the one declaration of
 // every launcher of gac_kernels.hip, gac_compose.hip, gac_axtout.hip, gac_depth.hip,
-// gac_prenet.hip and gac_axtfilter.hip (each includes this header, so its definitions are checked against it).
+// gac_prenet.hip, gac_axtfilter.hip and gac_axtpsl.hip (each includes this header, so its definitions are checked against it).
 // gfx950 only.
 //
 // HBM layout (see DESIGN.md "Data layout in HBM"):
@@ -19,6 +19,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "gachain.h"
 
 namespace gac {
 
@@ -502,5 +504,30 @@ struct AxtfArgs {
 };
 // enforces 1 <= window <= kAxtfMaxWindow (the tile bound) and the grid limit
 hipError_t launch_axt_filter(const AxtfArgs &a, int64_t chunks, hipStream_t s);
+
+// ---- gac_axtpsl.hip: axtToPsl's counts and blocks (gac_axt_psl).  A wave
+// walks an entry in tiles of kAxtpTile columns; the count pass writes the
+// entries' records and block counts, the emit pass (after the 64-bit scan of
+// the counts) the blocks at boff[i] on.
+constexpr int kAxtpTile = GAC_AXTPSL_TILE;
+struct AxtpEntry {
+    int64_t t, q;  // byte offsets of the rows in text
+    int32_t len;   // columns
+    int32_t pad;
+};
+static_assert(sizeof(AxtpEntry) == 24, "AxtpEntry layout");
+struct AxtpArgs {
+    const uint8_t *text;
+    int64_t text_bytes;
+    const AxtpEntry *ent;   // [n]
+    int64_t n;
+    gac_axtpsl_entry *out;  // [n] block0 is written by the emit pass (relative to the batch)
+    long long *nblk;        // [n + 1] blocks of every entry (the caller zeroes nblk[n])
+    const long long *boff;  // [n + 1] their exclusive scan
+    gac_axtpsl_block *blk;  // [nb]
+    int64_t nb;             // boff[n]: no block is written at or past it
+};
+hipError_t launch_axt_psl_count(const AxtpArgs &a, hipStream_t s);
+hipError_t launch_axt_psl_emit(const AxtpArgs &a, hipStream_t s);
 
 }  // namespace gac

@@ -166,6 +166,13 @@ int gac_axtf_check(int64_t n, const char *text, int64_t text_bytes, const int64_
 int32_t gac_axtf_mmin(double min_ident, int32_t window);
 double *gac_axtf_terms(int32_t window);
 
+/* gac_axt_psl's argument check (shared with gac_axt_psl_host), and a result
+ * handle with room for n entries and n_blocks blocks, uninitialised (NULL: out
+ * of memory; gac_axtpsl_free releases it) */
+int gac_axtpsl_check(int64_t n, const char *text, int64_t text_bytes, const int64_t *t_off,
+                     const int64_t *q_off, const int32_t *len, gac_axtpsl_result *const *out);
+gac_axtpsl_result *gac_axtpsl_alloc(int64_t n, int64_t n_blocks);
+
 /* ---- host view of a resident sequence (kept after gac_genome_finalize) ----
  * packed: 2 bits/base MSB-first (T=0 C=1 A=2 G=3); N runs merged and sorted. */
 typedef struct gac_seq_view {

@@ -77,3 +77,59 @@ void gt_write_psl(FILE *f, const gt_chains *c, int64_t i, const int64_t counts[4
     p = put_list(f, buf, cap, p, bt, nb, basic, '\n');
     fwrite(buf, 1, (size_t)(p - buf), f);
 }
+
+int gt_put_psl_align(gac_obuf *o, const gt_psl_align *a, const gac_axtpsl_entry *e,
+                     const gac_axtpsl_block *blk) {
+    const int minus = a->strand == '-';
+    const uint32_t qsize = (uint32_t)a->qsize;
+    uint32_t qstart = (uint32_t)a->qstart, qend = (uint32_t)a->qend;
+    uint32_t tstart = (uint32_t)a->tstart, tend = (uint32_t)a->tend;
+    if (minus) { /* reverseIntRange */
+        const uint32_t s = qstart;
+        qstart = qsize - qend, qend = qsize - s;
+    }
+    qstart += (uint32_t)e->q_head, tstart += (uint32_t)e->t_head; /* trimAlignment */
+    qend -= (uint32_t)e->q_tail, tend -= (uint32_t)e->t_tail;
+    if (qstart == qend || tstart == tend)
+        return 0;
+    const uint32_t qs = minus ? qsize - qend : qstart, ts = tstart;
+    const int64_t nb = e->n_blocks;
+    char *p = gac_obuf_reserve(o, a->qname_len + a->tname_len + 16 * 12 + 8 + (size_t)nb * 36);
+    if (!p)
+        gt_abort("Out of memory");
+    char *const p0 = p;
+    p = put(p, e->match, 1, '\t');
+    p = put(p, e->mis_match, 1, '\t');
+    p = put(p, e->rep_match, 1, '\t');
+    p = put(p, e->n_count, 1, '\t');
+    p = put(p, e->q_num_insert, 1, '\t');
+    p = put(p, e->q_base_insert, 0, '\t');
+    p = put(p, e->t_num_insert, 1, '\t');
+    p = put(p, e->t_base_insert, 0, '\t');
+    *p++ = a->strand;
+    *p++ = '\t';
+    memcpy(p, a->qname, a->qname_len);
+    p += a->qname_len;
+    *p++ = '\t';
+    p = put(p, qsize, 1, '\t');
+    p = put(p, qstart, 1, '\t');
+    p = put(p, qend, 1, '\t');
+    memcpy(p, a->tname, a->tname_len);
+    p += a->tname_len;
+    *p++ = '\t';
+    p = put(p, (uint32_t)a->tsize, 1, '\t');
+    p = put(p, tstart, 1, '\t');
+    p = put(p, tend, 1, '\t');
+    p = put(p, nb, 1, '\t');
+    for (int64_t b = 0; b < nb; ++b)
+        p = put(p, (uint32_t)blk[b].size, 1, ',');
+    *p++ = '\t';
+    for (int64_t b = 0; b < nb; ++b)
+        p = put(p, qs + (uint32_t)blk[b].q_adv, 1, ',');
+    *p++ = '\t';
+    for (int64_t b = 0; b < nb; ++b)
+        p = put(p, ts + (uint32_t)blk[b].t_adv, 1, ',');
+    *p++ = '\n';
+    o->n += (size_t)(p - p0);
+    return 1;
+}

@@ -1,10 +1,12 @@
 /* gac_pslout.h -- the PSL line of a chain, shared by chainToPsl and
  * chainToPslBasic (kent/src/hg/mouseStuff/chainToPsl/chainToPsl.c:130-176 and
- * pslTabOut, kent/src/lib/psl.c:175-254: the same 21 tab-separated columns). */
+ * pslTabOut, kent/src/lib/psl.c:175-254: the same 21 tab-separated columns),
+ * and the PSL line of an alignment's rows (axtToPsl). */
 #ifndef GAC_PSLOUT_H
 #define GAC_PSLOUT_H
 
 #include "gac_tool.h"
+#include "host/gac_host.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -18,6 +20,26 @@ extern "C" {
  * every number "%d".  For '-' qStart / qEnd are flipped with the header's
  * qSize; qStarts are the chain's own strand coordinates. */
 void gt_write_psl(FILE *f, const gt_chains *c, int64_t i, const int64_t counts[4], int basic);
+
+/* An axt record's header for gt_put_psl_align: the strand character, the
+ * names as they stand in the text, the sizes, and the coordinates as axtRead
+ * leaves them (starts zero-based, the query's on its own strand). */
+typedef struct gt_psl_align {
+    char strand;
+    const char *qname, *tname;
+    size_t qname_len, tname_len;
+    int32_t qsize, tsize, qstart, qend, tstart, tend;
+} gt_psl_align;
+
+/* pslTabOut of pslFromAlign's psl (kent/src/lib/psl.c:1716-1806), appended to
+ * o, from what gac_axt_psl returns for the record's rows (e, and blk = its
+ * blocks) with the reference's arithmetic: qStart / qEnd flipped to the plus
+ * strand for '-' (axtToPsl.c:74), moved by the trim in those coordinates,
+ * nothing appended (and 0 returned) when qStart == qEnd or tStart == tEnd
+ * after it, qStarts from the flipped-back qStart.  The numbers are the
+ * reference's 32-bit ints, printed "%u" except the two base-insert columns. */
+int gt_put_psl_align(gac_obuf *o, const gt_psl_align *a, const gac_axtpsl_entry *e,
+                     const gac_axtpsl_block *blk);
 
 #ifdef __cplusplus
 }

@@ -19,6 +19,8 @@ chainPreNet's chainUsed (chainPreNet.c:104)  Engine.prenet_keep(blk_off, t_seq, 
                                              prenet_keep_host(...): the reference's own pass
 filterAxtIdentityEntropy.py's checkAxt (:88) Engine.axt_filter(t_rows, q_rows, ident, entropy, W)
                                              axt_filter_host(...): the same on host threads
+pslFromAlign's column loop (psl.c:1716)      Engine.axt_psl(t_rows, q_rows)
+                                             axt_psl_host(...): the same on host threads
 axtScoreUngapped per block (axt.c:186-194)   Engine.score_blocks / score_text_blocks (caller text)
 cBlockFindCrossover (chainConnect.c:61-105)  Engine.crossovers / text_crossovers (caller text)
 chainBlocks' kd-tree DP (chainBlock.c:400)   Engine.chain_dp_blocks (total, predecessor per block)
@@ -286,6 +288,22 @@ class Engine:
                                    float(min_ident), float(min_entropy), int(window), _p(keep),
                                    C.byref(st)))
         return keep, _axt_filter_stats(st)
+
+    # ---- alignments to PSL blocks (axtToPsl)
+    def axt_psl(self, t_rows, q_rows):
+        """What pslFromAlign makes of alignments' rows (gac_axt_psl): t_rows
+        and q_rows are the target and query rows of the entries (bytes or str,
+        of equal length).  Returns (entries, blocks, stats): entries a
+        structured array [n] with the fields of gac_axtpsl_entry (the eight
+        counts, q_head, t_head, q_tail, t_tail, cols, n_blocks, block0),
+        blocks int32 [n_blocks, 3] of (q_adv, t_adv, size), stats: blocks,
+        columns, host_entries, batches, fell_back."""
+        text, t_off, q_off, ln = _axt_psl_args(t_rows, q_rows)
+        res = C.POINTER(_lib.AxtPslResult)()
+        st = _lib.AxtPslStats()
+        check(lib().gac_axt_psl(self.h, len(ln), text, len(text), _p(t_off), _p(q_off), _p(ln),
+                                C.byref(res), C.byref(st)))
+        return _axt_psl_result(res, st)
 
     # ---- alignment text (chainToAxt)
     @staticmethod
@@ -718,6 +736,53 @@ def axt_filter_host(t_rows, q_rows, min_ident: float, min_entropy: float, window
     return keep, _axt_filter_stats(st)
 
 
+AXT_PSL_ENTRY = np.dtype([(name, {C.c_uint32: np.uint32, C.c_int32: np.int32, C.c_int64: np.int64}[t])
+                          for name, t in _lib.AxtPslEntry._fields_])
+
+
+def _axt_psl_args(t_rows, q_rows):
+    rows = [[r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in side]
+            for side in (t_rows, q_rows)]
+    if len(rows[0]) != len(rows[1]):
+        raise ValueError("axt_psl: as many target rows as query rows")
+    n = len(rows[0])
+    ln = np.fromiter((len(q) for q in rows[1]), np.int32, n)
+    tl = np.fromiter((len(t) for t in rows[0]), np.int32, n)
+    if np.any(tl != ln):
+        raise ValueError("axt_psl: a target row and its query row of different lengths")
+    # t0 q0 t1 q1 ...
+    starts = np.concatenate([[0], np.cumsum(np.repeat(ln.astype(np.int64), 2))]).astype(np.int64)
+    text = b"".join(x for pair in zip(rows[0], rows[1]) for x in pair)
+    return text, np.ascontiguousarray(starts[0:2 * n:2]), np.ascontiguousarray(starts[1:2 * n:2]), ln
+
+
+def _axt_psl_result(res, st):
+    """copies of a gac_axtpsl_result's arrays; the handle is released"""
+    try:
+        r = res.contents
+        entries = np.zeros(r.n, AXT_PSL_ENTRY)
+        blocks = np.zeros((r.n_blocks, 3), np.int32)
+        if r.n:
+            C.memmove(entries.ctypes.data, r.entry, entries.nbytes)
+        if r.n_blocks:
+            C.memmove(blocks.ctypes.data, r.block, blocks.nbytes)
+    finally:
+        lib().gac_axtpsl_free(res)
+    return entries, blocks, dict(blocks=st.blocks, columns=st.columns, host_entries=st.host_entries,
+                                 batches=st.batches, fell_back=st.fell_back)
+
+
+def axt_psl_host(t_rows, q_rows, nthreads: int = 0):
+    """Engine.axt_psl's result by one sequential pass an entry on host threads
+    (gac_axt_psl_host; no device): (entries, blocks, stats)."""
+    text, t_off, q_off, ln = _axt_psl_args(t_rows, q_rows)
+    res = C.POINTER(_lib.AxtPslResult)()
+    st = _lib.AxtPslStats()
+    check(lib().gac_axt_psl_host(len(ln), text, len(text), _p(t_off), _p(q_off), _p(ln), int(nthreads),
+                                 C.byref(res), C.byref(st)))
+    return _axt_psl_result(res, st)
+
+
 def antirepeat_pass(score: float, match, rep: int, total: int, min_score: int = 5000) -> bool:
     """chainAntiRepeat's keep/drop decision for one chain from its composition
     (gac_antirepeat_pass: degeneracyFilter then repeatFilter; host only)."""
@@ -739,4 +804,4 @@ def twobit_mask_runs(path: str, name: str) -> Tuple[np.ndarray, np.ndarray]:
 
 __all__ = ["Engine", "ChainSet", "GapCosts", "read_score_scheme", "GAC_T", "GAC_Q",
            "antirepeat_pass", "twobit_mask_runs", "depth_count_host", "prenet_keep_host",
-           "axt_filter_host"]
+           "axt_filter_host", "axt_psl_host", "AXT_PSL_ENTRY"]

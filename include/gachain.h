@@ -45,6 +45,8 @@
  *                                                 kent/src/hg/mouseStuff/chainPreNet/chainPreNet.c:88-137
  *   gac_axt_filter        <- getSeqIdent + getEntropy + checkAxt + processHit's counts
  *                                                 src/filterAxtIdentityEntropy.py:32-69,88-110,144-162
+ *   gac_axt_psl           <- trimAlignment + accumCounts + pslFromAlign's column loop
+ *                                                 kent/src/lib/psl.c:1626-1806
  */
 #ifndef GACHAIN_H
 #define GACHAIN_H
@@ -66,8 +68,9 @@ extern "C" {
  * 4 = gac_net_write_ex and gac_net_release (chainNet frees a net under its writers).
  * 5 = gac_depth_count and gac_depth_count_host (netSyntenic).
  * 6 = gac_prenet_keep and gac_prenet_keep_host (chainPreNet).
- * 7 = gac_axt_filter and gac_axt_filter_host (filterAxtIdentityEntropy.py). */
-#define GAC_ABI_MINOR 7
+ * 7 = gac_axt_filter and gac_axt_filter_host (filterAxtIdentityEntropy.py).
+ * 8 = gac_axt_psl, gac_axt_psl_host and gac_axtpsl_free (axtToPsl). */
+#define GAC_ABI_MINOR 8
 
 /* return codes */
 #define GAC_OK 0
@@ -487,6 +490,78 @@ int gac_axt_filter_host(int64_t n, const char *text, int64_t text_bytes,
                         const int64_t *t_off, const int64_t *q_off, const int32_t *len,
                         double min_ident, double min_entropy, int32_t window, int nthreads,
                         uint8_t *keep, gac_axtfilter_stats *st);
+
+/* ---- alignments to PSL blocks (axtToPsl) -----------------------------------
+ * What pslFromAlign (kent/src/lib/psl.c:1716-1806, with trimAlignment :1634 and
+ * accumCounts :1680, PSL_IS_SOFTMASK set) makes of the two rows of an
+ * alignment, without names, sizes, strands or coordinates.  The entries are
+ * given as for gac_axt_filter: two rows of len[i] columns at text + t_off[i]
+ * (target) and text + q_off[i] (query).  A gap is one of '-' '.' '=' '_'.
+ *
+ * The trim drops the columns before the first and after the last column
+ * without a gap.  q_head / t_head count the dropped leading columns that hold a
+ * query / target character (the other row has a gap there), q_tail / t_tail
+ * the trailing ones; cols is what is left.  Over those columns, columns with a
+ * gap in both rows are skipped and are never a "previous" column; a column
+ * without a gap adds to n_count if either character is 'N', else, if the
+ * characters are equal after toupper, to rep_match if either is lower case
+ * and to match if not, else to mis_match; a column with a gap in the query
+ * adds to t_base_insert, and to t_num_insert if the previous column's query
+ * character was no gap (q_* likewise with the rows swapped).  A block is a run
+ * of columns without a gap that no one-sided column interrupts; block b of
+ * entry i is block[entry[i].block0 + b] = the query and target characters
+ * between the first kept column and the block's first column, and the
+ * block's columns.  An entry with no column left has one block (0, 0, 0), the
+ * one pslFromAlign's closing addBlock makes.  The caller adds its own
+ * coordinates: with qs / ts the strand coordinates of the first kept column,
+ * qStarts[b] = qs + q_adv, tStarts[b] = ts + t_adv, blockSizes[b] = size.
+ *
+ * The blocks are variable-length output, so the result is library-owned: the
+ * call allocates one gac_axtpsl_result holding entry[n] and block[n_blocks]
+ * (blocks in entry order) and hands it back in *out; gac_axtpsl_free releases
+ * it (NULL is allowed).  On an error *out is NULL.
+ *
+ * The device walks an entry in tiles of GAC_AXTPSL_TILE columns (DESIGN.md
+ * 7.15).  The entries go in batches whose text stays under
+ * GAC_AXTPSL_BATCH_BYTES (an environment knob; default as
+ * GAC_AXTF_BATCH_BYTES); an entry alone over that is converted by the host
+ * twin (fell_back 2).
+ *
+ * GAC_E_ARG: n < 0, a negative length or offset, a row reaching past
+ * text_bytes, a NULL array with n > 0, out NULL.  n == 0 returns GAC_OK and an
+ * empty result without a launch.  Host buffers, synchronous; needs neither
+ * genomes nor a scoring setup.  st may be NULL. */
+#define GAC_AXTPSL_TILE 512
+typedef struct gac_axtpsl_entry {
+    uint32_t match, mis_match, rep_match, n_count;
+    uint32_t q_num_insert, q_base_insert, t_num_insert, t_base_insert;
+    int32_t q_head, t_head, q_tail, t_tail; /* characters the trim dropped */
+    int32_t cols;                           /* columns left after the trim */
+    int32_t n_blocks;                       /* >= 1 */
+    int64_t block0;                         /* index of the entry's first block */
+} gac_axtpsl_entry;
+typedef struct gac_axtpsl_block {
+    int32_t q_adv, t_adv, size;
+} gac_axtpsl_block;
+typedef struct gac_axtpsl_result {
+    int64_t n, n_blocks;
+    gac_axtpsl_entry *entry; /* [n] */
+    gac_axtpsl_block *block; /* [n_blocks] */
+} gac_axtpsl_result;
+typedef struct gac_axtpsl_stats {
+    int64_t blocks, columns;    /* blocks returned; columns given */
+    int64_t host_entries;       /* entries converted by the host twin */
+    int32_t batches, fell_back; /* 0 device; 2 some entry over the byte budget (those entries on the host) */
+} gac_axtpsl_stats;
+int gac_axt_psl(gac_ctx *ctx, int64_t n, const char *text, int64_t text_bytes,
+                const int64_t *t_off, const int64_t *q_off, const int32_t *len,
+                gac_axtpsl_result **out, gac_axtpsl_stats *st);
+/* The same result by one sequential pass an entry on nthreads host threads
+ * (<= 0: GAC_THREADS, else all CPUs); no device (axtToPsl -host, the fallback). */
+int gac_axt_psl_host(int64_t n, const char *text, int64_t text_bytes, const int64_t *t_off,
+                     const int64_t *q_off, const int32_t *len, int nthreads,
+                     gac_axtpsl_result **out, gac_axtpsl_stats *st);
+void gac_axtpsl_free(gac_axtpsl_result *r);
 
 /* ---- alignment text (chainToAxt) ------------------------------------------
  * A piece is a window of consecutive blocks of one chain (gac_window: chain,
@@ -952,7 +1027,8 @@ int gac_synchronize(gac_ctx *ctx);
 #define GAC_K_DEPTH 3    /* gac_depth_count: events, sort, scans, counts (one lap per call) */
 #define GAC_K_PRENET 4   /* gac_prenet_keep: every pass's fill, scans, mark and check (one lap per call) */
 #define GAC_K_AXTFILTER 5 /* gac_axt_filter: the window kernel (one lap per batch) */
-#define GAC_K_COUNT 6
+#define GAC_K_AXTPSL 6    /* gac_axt_psl: count, scan and emit (one lap per batch) */
+#define GAC_K_COUNT 7
 #define GAC_PROF_ALL ((1 << GAC_K_COUNT) - 1)
 /* Event timing of each launch of the kernels in `mask` (bits 1 << GAC_K_*;
  * 0 = off, GAC_PROF_ALL = all).  Each timed kernel adds two event markers
