@@ -373,7 +373,11 @@ int gac_chain_psl_counts_device(gac_ctx *ctx, const gac_chainset *cs, int64_t *d
  * (dupeTreeAddSub / dupeTreeCountOver,
  * kent/src/hg/mouseStuff/netSyntenic/netSyntenic.c:63-138) for every range at
  * once; ranges of length 0 count 0.  Sequence ids are any non-negative
- * numbers (sparse is fine).  Exact integers.  GAC_E_ARG: end < start, a
+ * numbers (sparse is fine).  Exact integers, within one bound that is not
+ * checked: the running depth is an int32_t, here and in the host twin, so the
+ * sum of |delta[j]| over the ranges covering or touching any one position of
+ * a sequence must stay below 2^31 (it does for any n this call takes when
+ * delta is +-1).  GAC_E_ARG: end < start, a
  * negative seq or start, threshold < 1, or more than INT32_MAX / 2 ranges.
  * n == 0 returns GAC_OK without a launch.  Host buffers, synchronous; needs
  * neither genomes nor a scoring setup. */

@@ -11,7 +11,10 @@ restatement equals the reference binary before it writes a fixture).
   net_syntenic(text)     the three together: the tool's output
   depth_count            the coverage count by sort and cumsum
   depth_count_brute      the same per base (small coordinate spaces)
-  SHAPES, BAD_ARGS       the coverage count's test inputs
+  SHAPES, BAD_ARGS       the coverage count's test inputs, with
+  shape_id_width, shape_delta_range, random_small_cases (the small inputs of
+                         the per-base checks) and stride_net_text (a net of
+                         more records than one grid of the depth kernels)
 """
 import os
 import re
@@ -267,8 +270,147 @@ def shape_wide():
     return seq, np.zeros(8, np.int64), np.full(8, 2**31 - 1), np.ones(8, np.int64)
 
 
+STRIDE_N = 2048 * 256 + 77  # one full grid of ranges (two of range ends) and a tail
+
+
+def shape_stride():
+    """524 365 ranges (1 048 730 events) over 5 sequences: more than the
+    kernels' largest grid (2048 workgroups of 256) holds, so the loops over
+    the events take a second full trip and a third for the last 154, and the
+    loop over the ranges a second for the last 77"""
+    rng = np.random.default_rng(21)
+    n = STRIDE_N
+    seq = rng.integers(0, 5, n)
+    start = rng.integers(0, 1 << 20, n)
+    end = start + rng.integers(1, 3000, n)
+    end[::10] = start[::10]
+    delta = np.where(rng.random(n) < 0.3, -1, 1)
+    return seq, start, end, delta
+
+
+def _ties(positions, ids, n=3000, seed=22):
+    rng = np.random.default_rng(seed)
+    pos = np.asarray(positions, np.int64)
+    a, b = pos[rng.integers(0, len(pos), n)], pos[rng.integers(0, len(pos), n)]
+    seq = np.asarray(ids, np.int64)[rng.integers(0, len(ids), n)]
+    delta = rng.choice([-1, 1, 1], n)
+    return seq, np.minimum(a, b), np.maximum(a, b), delta
+
+
+def shape_ties():
+    """3000 ranges whose starts and ends all lie on 0, 7, 8, 2^31 - 2 and
+    2^31 - 1 of the sequences 0 and 2^31 - 1: many starts, ends and
+    zero-length ranges of mixed sign on each position"""
+    return _ties([0, 7, 8, 2**31 - 2, 2**31 - 1], [0, 2**31 - 1])
+
+
+def shape_ties_small():
+    """the same on positions 0, 7, 8, 40 and 41, small enough for the
+    per-base count"""
+    return _ties([0, 7, 8, 40, 41], [0, 2**31 - 1])
+
+
+def ties_thresholds():
+    """the depths, counted per base, that the stretches between ties_small's
+    positions lie under (ties' are the same, drawn alike), and each plus 1:
+    at threshold 2 every stretch is far above it, at these the counts change"""
+    seq, start, end, delta = shape_ties_small()
+    found = set()
+    for s in np.unique(seq):
+        depth = np.zeros(41, np.int64)
+        for i in np.nonzero(seq == s)[0]:
+            depth[start[i]:end[i]] += delta[i]
+        found |= {int(d) for d in depth if d >= 1}
+    return sorted(found | {d + 1 for d in found})
+
+
+def shape_id_width(k):
+    """seven overlapping ranges on the sequence ids 2^k, 2^k - 1 and 0: the
+    largest id is an exact power of two, bit k is the sort key's top bit, and
+    without it the ranges of id 2^k fall on those of id 0"""
+    hi = 1 << k
+    seq = [hi, hi - 1, 0, hi, hi - 1, hi, 0]
+    start = [0, 50, 10, 40, 60, 99, 90]
+    end = [100, 150, 95, 100, 70, 400, 91]
+    return seq, start, end, [1] * 7
+
+
+ID_WIDTHS = range(31)
+
+DELTA_THRESHOLDS = (1, 2, 127, 128, 255, 1000, 2**31 - 1)
+
+
+def shape_delta_range():
+    """500 ranges on 2 sequences below position 420 with deltas over the
+    whole int8 range, -128 (whose negation is no int8) and 0 among them"""
+    rng = np.random.default_rng(22)
+    n = 500
+    seq = rng.integers(0, 2, n)
+    start = rng.integers(0, 300, n)
+    end = start + rng.integers(0, 120, n)
+    delta = rng.choice([-128, -127, -2, -1, 0, 1, 2, 127], n)
+    return seq, start, end, delta
+
+
+def random_small_cases():
+    """the 200 random cases (n < 40, 3 sequences, positions below 90) of the
+    restatement's own check against the per-base count"""
+    rng = np.random.default_rng(5)
+    for _ in range(200):
+        n = int(rng.integers(1, 40))
+        seq = rng.integers(0, 3, n)
+        start = rng.integers(0, 60, n)
+        end = start + rng.integers(0, 30, n)
+        delta = rng.choice([-2, -1, 1, 1, 1, 3], n)
+        yield seq, start, end, delta
+
+
 SHAPES = {"ref_test": shape_ref_test_block, "dense": shape_dense, "sparse": shape_sparse,
-          "wide": shape_wide}
+          "wide": shape_wide, "stride": shape_stride, "ties": shape_ties,
+          "ties_small": shape_ties_small}
+
+def stride_net_text(tops_per_net=3100):
+    """A net file of 3 nets and 29 records per top-level fill (269 700 with the
+    default, more than the 262 144 one grid of the depth kernels takes), four
+    levels deep, over the query names chrA..chrD: a fill, its 4 gaps (one in
+    eight of query size 0), 2 fills in each (one in four placed anywhere on
+    any query name), a gap in each of those and a fill in that, placed
+    anywhere.  Returns (text, the text of its first net, records)."""
+    rng = np.random.default_rng(23)
+    names = ["chrA", "chrB", "chrC", "chrD"]
+    out, first_len, fid = [], 0, 0
+
+    def anywhere(size):
+        return names[rng.integers(0, 4)], "+-"[rng.integers(0, 2)], int(rng.integers(0, 1 << 25)), size
+
+    def fill(level, t, t_size, q):
+        nonlocal fid
+        fid += 1
+        out.append(f"{' ' * level}fill {t} {t_size} {q[0]} {q[1]} {q[2]} {q[3]} id {fid} "
+                   f"score {1000 + fid % 977} ali {max(t_size - 3, 1)}\n")
+
+    def gap(level, t, t_size, q):
+        out.append(f"{' ' * level}gap {t} {t_size} {q[0]} {q[1]} {q[2]} {q[3]}\n")
+
+    for net in range(3):
+        out.append(f"net chr{net + 1} {tops_per_net * 20000}\n")
+        for j in range(tops_per_net):
+            t0 = j * 20000
+            name, strand, q0, _ = top = anywhere(16000)
+            fill(1, t0, 16000, top)
+            for g in range(4):
+                tg, qg = t0 + 1000 + g * 3500, q0 + 1000 + g * 3500
+                gap(2, tg, 3000, (name, strand, qg, 0 if rng.integers(0, 8) == 0 else 3000))
+                for c in range(2):
+                    tc, qc = tg + 200 + c * 1400, qg + 200 + c * 1400
+                    child = anywhere(1000) if rng.integers(0, 4) == 0 else (name, strand, qc, 1000)
+                    fill(3, tc, 1000, child)
+                    gap(4, tc + 300, 400, (child[0], child[1], child[2] + 300, 400))
+                    fill(5, tc + 400, 200, anywhere(200))
+        if net == 0:
+            first_len = len(out)
+    return "".join(out), "".join(out[:first_len]), len(out) - 3
+
 
 BAD_ARGS = {  # each GAC_E_ARG case: (seq, start, end, delta, threshold)
     "end_before_start": ([0, 0], [5, 9], [6, 8], [1, 1], 2),

@@ -1,12 +1,19 @@
 """netSyntenic on the GPU: Engine.depth_count (gac_depth_count: events, sort,
-depth scan, covered-length scan) against the numpy restatement
-(tests/netsyn_ref.py) on the shapes of tests/test_netsyn_cpu.py, its argument
-checks, and the default (device) tool byte for byte against the reference's
-outputs and against the reference binary run here.  Every comparison is
-exact."""
+depth scan, covered-length scan) against the numpy restatement and the
+per-base count (tests/netsyn_ref.py), never against itself, on the shapes of
+tests/test_netsyn_cpu.py: more ranges than one grid of the kernels holds
+(`stride`), 31 widths of the sort key, deltas over the whole int8 range under
+thresholds up to 2^31 - 1, starts, ends and zero-length ranges piled on five
+positions up to 2^31 - 1, 200 tiny random inputs; that a call writes count[0..n)
+and nothing else, is one GAC_K_DEPTH lap, and holds up from two threads on one
+context; its argument checks; and the default (device) tool byte for byte
+against the reference's outputs, the reference binary run here and, on a net
+of more records than one grid, the -host tool and the restatement.  Every
+comparison is exact."""
 import ctypes as C
 import os
 import subprocess
+import threading
 
 import numpy as np
 import pytest
@@ -39,13 +46,115 @@ def test_empty_and_single(engine):
     assert engine.depth_count([7], [3], [3], [1], 1).tolist() == [0]
 
 
-@pytest.mark.parametrize("shape", ["dense", "sparse", "wide"])
+@pytest.mark.parametrize("shape", sorted(NS.SHAPES))
 def test_shapes(engine, expected, shape):
     got = engine.depth_count(*NS.SHAPES[shape](), 2)
     assert got.dtype == np.int32
     assert np.array_equal(got, expected[shape])
     if shape == "wide":  # the covered lengths sum to 4 * (2^31 - 1) > 2^32
         assert got.tolist() == [2**31 - 1] * 8
+    if shape == "stride":  # the ranges only a second trip of k_depth_out's loop reaches
+        assert len(got) == 2048 * 256 + 77 and expected[shape][-77:].any()
+    if shape == "ties":
+        assert expected[shape].max() == 2**31 - 1 and len(np.unique(expected[shape])) > 5
+    if shape == "ties_small":
+        assert np.array_equal(got, NS.depth_count_brute(*NS.SHAPES[shape](), 2))
+
+
+def test_ties_at_their_own_depths(engine):
+    """`ties` and `ties_small` at the depths their stretches lie under and one
+    above each: at threshold 2 every stretch counts, at these the signs of
+    the piled-up events decide"""
+    small, large = NS.shape_ties_small(), NS.shape_ties()
+    for thr in NS.ties_thresholds():
+        assert np.array_equal(engine.depth_count(*small, thr), NS.depth_count_brute(*small, thr)), thr
+        assert np.array_equal(engine.depth_count(*large, thr), NS.depth_count(*large, thr)), thr
+
+
+@pytest.mark.parametrize("k", NS.ID_WIDTHS)
+def test_sequence_id_widths(engine, k):
+    """the sort's end_bit at 33 + k, with the largest id the power of two 2^k:
+    a key one bit short puts id 2^k on id 0 and changes the counts"""
+    a = NS.shape_id_width(k)
+    want = NS.depth_count(*a, 2)
+    assert not np.array_equal(want, NS.depth_count(np.asarray(a[0]) & ~(1 << k), *a[1:], 2))
+    got = engine.depth_count(*a, 2)
+    assert np.array_equal(got, want)
+    assert np.array_equal(got, NS.depth_count_brute(*a, 2))
+
+
+@pytest.mark.parametrize("thr", NS.DELTA_THRESHOLDS)
+def test_delta_range_and_thresholds(engine, thr):
+    a = NS.shape_delta_range()
+    want = NS.depth_count_brute(*a, thr)
+    assert want.any() == (thr <= 255)  # (102 counts are not 0 at 1, 77 at 255, none at 1000)
+    assert np.array_equal(engine.depth_count(*a, thr), want)
+
+
+def test_random_small_vs_per_base(engine):
+    """the restatement's own 200 random cases, at thresholds 1, 2 and 3"""
+    cases = 0
+    for a in NS.random_small_cases():
+        for thr in (1, 2, 3):
+            assert np.array_equal(engine.depth_count(*a, thr), NS.depth_count_brute(*a, thr))
+        cases += 1
+    assert cases == 200
+
+
+@pytest.mark.parametrize("n", [1000, 1])
+def test_writes_count_only(engine, n):
+    """a raw call: count[0..n) is written, the 64 words on either side of it
+    and the four input arrays are not"""
+    from genomealignmenttools_amd._lib import lib
+    seq, start, end, delta = (x[:n] for x in NS.shape_dense()) if n > 1 else ([5], [3], [9], [2])
+    arrays = [np.ascontiguousarray(x, t) for x, t in
+              ((seq, np.int32), (start, np.int32), (end, np.int32), (delta, np.int8))]
+    kept = [x.copy() for x in arrays]
+    guard = np.int32(-0x5A5A5A5B)
+    buf = np.full(64 + n + 64, guard, np.int32)
+    rc = lib().gac_depth_count(engine.h, n, *(C.c_void_p(x.ctypes.data) for x in arrays), 2,
+                               C.c_void_p(buf.ctypes.data + 64 * 4))
+    assert rc == 0
+    assert (buf[:64] == guard).all() and (buf[64 + n:] == guard).all()
+    for x, y in zip(arrays, kept):
+        assert np.array_equal(x, y)
+    want = NS.depth_count(*kept, 2)
+    assert want.any()
+    assert np.array_equal(buf[64:64 + n], want)
+
+
+def test_kernel_timing_is_one_lap_per_call(engine):
+    from genomealignmenttools_amd._lib import GAC_K_DEPTH
+    a = NS.shape_ref_test_block()
+    engine.prof_enable(True, kernels=[GAC_K_DEPTH])
+    engine.prof_reset()
+    try:
+        engine.depth_count(*a, 2)
+        ms, laps = engine.prof_read(GAC_K_DEPTH)
+    finally:
+        engine.prof_enable(False)
+    assert laps == 1 and ms > 0
+
+
+def test_two_threads_one_context(engine, expected):
+    """ten calls each from two threads on one engine: the context's lock keeps
+    a call's buffers and stream work its own"""
+    got = {"dense": [], "ties_small": []}
+
+    def run(shape):
+        a = NS.SHAPES[shape]()
+        for _ in range(10):
+            got[shape].append(engine.depth_count(*a, 2))
+
+    threads = [threading.Thread(target=run, args=(shape,)) for shape in got]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    for shape, results in got.items():
+        assert len(results) == 10
+        for r in results:
+            assert np.array_equal(r, expected[shape]), shape
 
 
 @pytest.mark.parametrize("case", sorted(NS.BAD_ARGS))
@@ -90,3 +199,29 @@ def test_tool_device_equals_reference_binary(tmp_path):
     r = subprocess.run([ref, src, theirs], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr
     assert open(ours, "rb").read() == open(theirs, "rb").read()
+
+
+def test_tool_more_records_than_one_grid(tmp_path):
+    """A net written here of 269 700 records (3 nets, four levels, four query
+    names), so that the tool's one call takes a second trip of every loop over
+    the events: the device tool and -host give the same bytes at full size.
+    The restatement takes 7.8 s on that text on the CPU (4.3 s of it the
+    parse), so it is compared on the first net of the file only (89 900
+    records, 1.7 s), run through the device tool as a file of its own: whole
+    output, every fill's qDup with it."""
+    text, first, records = NS.stride_net_text()
+    assert records > 2048 * 256 // 2 and text.startswith(first)
+    outs = {}
+    for name, body, opts in (("whole", text, []), ("whole_host", text, ["-host"]), ("first", first, [])):
+        src, out = str(tmp_path / (name + ".net")), str(tmp_path / (name + ".syn.net"))
+        with open(src, "w") as f:
+            f.write(body)
+        r = subprocess.run([_tool()] + opts + [src, out], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        outs[name] = open(out, "rb").read()
+    assert outs["whole"] == outs["whole_host"]
+    assert outs["whole"].count(b" qDup ") == outs["whole"].count(b" fill ") > records // 2
+    want = NS.net_syntenic(first)
+    fills, zeros = want.count(" qDup "), want.count(" qDup 0 ")
+    assert fills == first.count(" fill ") and 10000 < zeros < fills - 10000  # (29 137 of 52 700)
+    assert outs["first"] == want.encode()

@@ -1,6 +1,10 @@
 """netSyntenic without a GPU: the coverage count's restatement against a
-per-base count, the host twin (gac_depth_count_host) against the restatement,
-bin/netSyntenic -host byte for byte against the reference's outputs
+per-base count (random cases, tied positions, the whole int8 range of deltas
+under thresholds up to 2^31 - 1, 31 widths of the sequence id), the host twin
+(gac_depth_count_host) against the restatement on every shape of
+netsyn_ref.SHAPES (`stride` and `ties` among them, whose positions are too
+many or too large for the per-base count) and against the per-base count on
+the small inputs, bin/netSyntenic -host byte for byte against the reference's outputs
 (tests/golden/make_netsyn_golden.py), the reference's error messages, the new
 symbols, and the pipeline netSyntenic | NetFilterNonNested.perl.  Every
 comparison is exact."""
@@ -38,19 +42,29 @@ def expected():
 
 
 def test_restatement_equals_brute_force():
-    rng = np.random.default_rng(5)
-    for _ in range(200):
-        n = int(rng.integers(1, 40))
-        seq = rng.integers(0, 3, n)
-        start = rng.integers(0, 60, n)
-        end = start + rng.integers(0, 30, n)
-        delta = rng.choice([-2, -1, 1, 1, 1, 3], n)
+    cases = 0
+    for seq, start, end, delta in NS.random_small_cases():
         for thr in (1, 2, 3):
             assert np.array_equal(NS.depth_count(seq, start, end, delta, thr),
                                   NS.depth_count_brute(seq, start, end, delta, thr))
-    a = shape_ref_test_block()
-    for thr in (1, 2, 3):
-        assert np.array_equal(NS.depth_count(*a, thr), NS.depth_count_brute(*a, thr))
+        cases += 1
+    assert cases == 200
+    for a in (shape_ref_test_block(), NS.shape_ties_small()):
+        for thr in (1, 2, 3):
+            assert np.array_equal(NS.depth_count(*a, thr), NS.depth_count_brute(*a, thr))
+    a = NS.shape_delta_range()
+    nonzero = {}
+    for thr in NS.DELTA_THRESHOLDS:
+        want = NS.depth_count_brute(*a, thr)
+        assert np.array_equal(NS.depth_count(*a, thr), want)
+        nonzero[thr] = int((want != 0).sum())
+    assert nonzero[1] > nonzero[255] > 0 and nonzero[1000] == 0
+    for k in NS.ID_WIDTHS:
+        a = NS.shape_id_width(k)
+        want = NS.depth_count_brute(*a, 2)
+        assert np.array_equal(NS.depth_count(*a, 2), want)
+        # without bit k, sequence 2^k falls on sequence 0 and the counts change
+        assert not np.array_equal(NS.depth_count(np.asarray(a[0]) & ~(1 << k), *a[1:], 2), want)
     assert NS.depth_count(*shape_wide(), 2).tolist() == [2**31 - 1] * 8
     assert NS.depth_count(*shape_wide(), 3).tolist() == [0] * 8
 
@@ -64,6 +78,37 @@ def test_host_twin_equals_restatement(expected, shape):
             assert np.array_equal(_host(*a, thr), NS.depth_count_brute(*a, thr))
     if shape == "dense":
         assert expected[shape].max() > 0 and (expected[shape] == 0).sum() > 7000
+    if shape == "stride":
+        assert len(a[0]) == 2048 * 256 + 77 and expected[shape][-77:].any()
+    if shape == "ties":  # (positions too large for the per-base count)
+        assert (a[1] == a[2]).sum() > 300 and expected[shape].max() == 2**31 - 1
+        assert len(np.unique(expected[shape])) > 5
+    if shape == "ties_small":
+        assert np.array_equal(expected[shape], NS.depth_count_brute(*a, 2))
+
+
+def test_host_twin_edges_equal_per_base_count():
+    """the device tests' small inputs through the host twin: the whole int8
+    range of deltas under every threshold, the 31 key widths, the 200 random
+    cases"""
+    a = NS.shape_delta_range()
+    for thr in NS.DELTA_THRESHOLDS:
+        assert np.array_equal(_host(*a, thr), NS.depth_count_brute(*a, thr)), thr
+    for k in NS.ID_WIDTHS:
+        a = NS.shape_id_width(k)
+        assert np.array_equal(_host(*a, 2), NS.depth_count_brute(*a, 2)), k
+    for a in NS.random_small_cases():
+        for thr in (1, 2, 3):
+            assert np.array_equal(_host(*a, thr), NS.depth_count_brute(*a, thr))
+    # the tied positions at the depths their stretches lie under, where the counts change
+    small, large, seen = NS.shape_ties_small(), NS.shape_ties(), set()
+    for thr in NS.ties_thresholds():
+        want = NS.depth_count_brute(*small, thr)
+        assert np.array_equal(NS.depth_count(*small, thr), want)
+        assert np.array_equal(_host(*small, thr), want), thr
+        assert np.array_equal(_host(*large, thr), NS.depth_count(*large, thr)), thr
+        seen.add(want.tobytes())
+    assert len(seen) > 4
 
 
 def test_host_twin_small_and_bad_arguments():
