@@ -23,9 +23,9 @@ HOST_SRC := $(wildcard $(CSRC)/host/*.c)
 HOST_OBJ := $(patsubst $(CSRC)/host/%.c,$(OBJDIR)/host/%.o,$(HOST_SRC))
 # kernels and their launchers, then the C ABI by subject (gac_device.hip:
 # scoring; gac_abi_*.hip; all over gac_ctx.h), then the rank communicator
-HIP_SRC  := $(CSRC)/gac_kernels.hip $(CSRC)/gac_compose.hip $(CSRC)/gac_axtout.hip $(CSRC)/gac_depth.hip $(CSRC)/gac_prenet.hip $(CSRC)/gac_axtfilter.hip $(CSRC)/gac_axtpsl.hip $(CSRC)/gac_dp.hip $(CSRC)/gac_dptree.hip \
+HIP_SRC  := $(CSRC)/gac_kernels.hip $(CSRC)/gac_compose.hip $(CSRC)/gac_axtout.hip $(CSRC)/gac_depth.hip $(CSRC)/gac_prenet.hip $(CSRC)/gac_axtfilter.hip $(CSRC)/gac_axtpsl.hip $(CSRC)/gac_axtscore.hip $(CSRC)/gac_dp.hip $(CSRC)/gac_dptree.hip \
             $(CSRC)/gac_abi_context.hip $(CSRC)/gac_abi_genome.hip $(CSRC)/gac_abi_chains.hip $(CSRC)/gac_device.hip \
-            $(CSRC)/gac_abi_dp.hip $(CSRC)/gac_abi_seqout.hip $(CSRC)/gac_abi_depth.hip $(CSRC)/gac_abi_prenet.hip $(CSRC)/gac_abi_axtfilter.hip $(CSRC)/gac_abi_axtpsl.hip $(CSRC)/gac_comm.hip
+            $(CSRC)/gac_abi_dp.hip $(CSRC)/gac_abi_seqout.hip $(CSRC)/gac_abi_depth.hip $(CSRC)/gac_abi_prenet.hip $(CSRC)/gac_abi_axtfilter.hip $(CSRC)/gac_abi_axtpsl.hip $(CSRC)/gac_abi_axtscore.hip $(CSRC)/gac_comm.hip
 HIP_OBJ  := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(HIP_SRC))
 HDRS     := include/gachain.h $(CSRC)/gac_kernels.h $(CSRC)/gac_dp.h $(CSRC)/gac_ctx.h $(wildcard $(CSRC)/host/*.h)
 
@@ -36,10 +36,10 @@ EXECDIR  := $(PKG)/libexec
 # by blit kernels instead of the SDMA engines (HSA_ENABLE_SDMA=0: 20 vs 13
 # GB/s for the genome uploads on the box, profiles/r02f_*), and execs it --
 # before anything touches the GPU.  Either can be overridden from outside.
-# NetFilterNonNested.perl, chainSort, chainMergeSort and chainToPslBasic are
-# host-only: in bin/.
-GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt netToAxt chainToPsl netSyntenic chainPreNet filterAxtIdentityEntropy.py axtToPsl
-HOST_TOOLS := NetFilterNonNested.perl chainSort chainMergeSort chainToPslBasic
+# NetFilterNonNested.perl, chainSort, chainMergeSort, chainToPslBasic and
+# axtSort are host-only: in bin/.
+GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt netToAxt chainToPsl netSyntenic chainPreNet filterAxtIdentityEntropy.py axtToPsl axtToMaf
+HOST_TOOLS := NetFilterNonNested.perl chainSort chainMergeSort chainToPslBasic axtSort
 TOOLS    := $(addprefix $(EXECDIR)/,$(GPU_TOOLS)) $(addprefix $(BINDIR)/,$(GPU_TOOLS)) \
             $(addprefix $(BINDIR)/,$(HOST_TOOLS))
 TOOL_LIB_SRC := $(wildcard $(CSRC)/tools/lib/*.c)
@@ -79,7 +79,7 @@ $(BINDIR)/NetFilterNonNested.perl: $(CSRC)/tools/NetFilterNonNested.perl.c $(TOO
 	$(CC) $(CFLAGS) -I$(CSRC)/tools/lib $< $(TOOL_LIB_OBJ) -o $@ -L$(LIBDIR) -lgachain \
 	    -Wl,-rpath,'$$ORIGIN/../lib' -lz -lm -lpthread
 
-$(BINDIR)/chainSort $(BINDIR)/chainMergeSort $(BINDIR)/chainToPslBasic: $(BINDIR)/%: $(CSRC)/tools/%.c $(TOOL_LIB_OBJ) $(LIBDIR)/libgachain.so $(HDRS)
+$(BINDIR)/chainSort $(BINDIR)/chainMergeSort $(BINDIR)/chainToPslBasic $(BINDIR)/axtSort: $(BINDIR)/%: $(CSRC)/tools/%.c $(TOOL_LIB_OBJ) $(LIBDIR)/libgachain.so $(HDRS)
 	@mkdir -p $(BINDIR)
 	$(CC) $(CFLAGS) -I$(CSRC)/tools/lib $< $(TOOL_LIB_OBJ) -o $@ -L$(LIBDIR) -lgachain \
 	    -Wl,-rpath,'$$ORIGIN/../lib' -lz -lm -lpthread

@@ -27,10 +27,12 @@ GAC_Q = 1
 GAC_WANT_LOCAL = 1
 GAC_K_PLAN, GAC_K_TILE, GAC_K_COMBINE, GAC_K_DEPTH, GAC_K_PRENET, GAC_K_AXTFILTER = 0, 1, 2, 3, 4, 5
 GAC_K_AXTPSL = 6
+GAC_K_AXTSCORE = 7
 GAC_PRENET_MAX_ROUNDS = 32
 GAC_PRENET_ON_DEVICE, GAC_PRENET_FELL_ROUNDS, GAC_PRENET_FELL_MEMORY = 0, 1, 2
 GAC_AXTF_MAX_WINDOW = 1024
 GAC_AXTPSL_TILE = 512
+GAC_AXTSCORE_CHUNK = 1024
 
 _lock = threading.Lock()
 _lib = None
@@ -141,6 +143,11 @@ class AxtPslStats(C.Structure):
                 ("batches", C.c_int32), ("fell_back", C.c_int32)]
 
 
+class AxtScoreStats(C.Structure):
+    _fields_ = [("columns", C.c_int64), ("host_entries", C.c_int64),
+                ("batches", C.c_int32), ("fell_back", C.c_int32)]
+
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "gac_abi_version": (C.c_int, []),
@@ -220,6 +227,12 @@ _PROTOS = {
         C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                   C.POINTER(C.POINTER(AxtPslResult)), C.c_void_p]),
     "gac_axtpsl_free": (None, [C.POINTER(AxtPslResult)]),
+    "gac_axt_score": (
+        C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                  C.c_void_p, C.c_void_p]),
+    "gac_axt_score_host": (
+        C.c_int, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                  C.c_void_p, C.c_void_p]),
     "gac_antirepeat_pass": (
         C.c_int, [C.c_double, C.POINTER(C.c_int64), C.c_int64, C.c_int64, C.c_int]),
     "gac_abi_minor": (C.c_int, []),

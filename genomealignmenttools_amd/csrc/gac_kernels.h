@@ -1,7 +1,7 @@
 // gac_kernels.h -- device data layout shared by the HIP kernels and the
 // C-ABI implementation (gac_device.hip and the gac_abi_*.hip units), and the one declaration of
 // every launcher of gac_kernels.hip, gac_compose.hip, gac_axtout.hip, gac_depth.hip,
-// gac_prenet.hip, gac_axtfilter.hip and gac_axtpsl.hip (each includes this header, so its definitions are checked against it).
+// gac_prenet.hip, gac_axtfilter.hip, gac_axtpsl.hip and gac_axtscore.hip (each includes this header, so its definitions are checked against it).
 // gfx950 only.
 //
 // HBM layout (see DESIGN.md "Data layout in HBM"):
@@ -529,5 +529,27 @@ struct AxtpArgs {
 };
 hipError_t launch_axt_psl_count(const AxtpArgs &a, hipStream_t s);
 hipError_t launch_axt_psl_emit(const AxtpArgs &a, hipStream_t s);
+
+// ---- gac_axtscore.hip: axtScoreSym under the default scheme (gac_axt_score).
+// The unit of work is a chunk: up to kAxtsChunk consecutive columns of one
+// entry, summed by one wave.  launch_axt_score_chunks writes every entry's
+// number of chunks, the shared 64-bit scan (dt_scan64) turns them into first
+// chunks, and launch_axt_score adds each chunk's sum into its entry's score.
+constexpr int kAxtsChunk = GAC_AXTSCORE_CHUNK;
+struct AxtsEntry {
+    int64_t t, q;  // row offsets into the batch's text
+    int32_t len, pad;
+};
+static_assert(sizeof(AxtsEntry) == 24, "AxtsEntry layout");
+struct AxtsArgs {
+    const uint8_t *text;
+    int64_t text_bytes, n;
+    const AxtsEntry *ent;      // [n]
+    long long *nchunk;         // [n + 1] written by the chunks pass; [n] zeroed by the caller
+    const long long *chunk0;   // [n + 1] exclusive scan of nchunk
+    uint32_t *score;           // [n] zeroed by the caller; sums modulo 2^32
+};
+hipError_t launch_axt_score_chunks(const AxtsArgs &a, hipStream_t s);
+hipError_t launch_axt_score(const AxtsArgs &a, int64_t chunks, hipStream_t s);
 
 }  // namespace gac

@@ -173,6 +173,10 @@ int gac_axtpsl_check(int64_t n, const char *text, int64_t text_bytes, const int6
                      const int64_t *q_off, const int32_t *len, gac_axtpsl_result *const *out);
 gac_axtpsl_result *gac_axtpsl_alloc(int64_t n, int64_t n_blocks);
 
+/* gac_axt_score's argument check (shared with gac_axt_score_host) */
+int gac_axtscore_check(int64_t n, const char *text, int64_t text_bytes, const int64_t *t_off,
+                       const int64_t *q_off, const int32_t *len, const int32_t *score);
+
 /* ---- host view of a resident sequence (kept after gac_genome_finalize) ----
  * packed: 2 bits/base MSB-first (T=0 C=1 A=2 G=3); N runs merged and sorted. */
 typedef struct gac_seq_view {

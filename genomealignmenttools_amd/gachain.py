@@ -21,6 +21,8 @@ filterAxtIdentityEntropy.py's checkAxt (:88) Engine.axt_filter(t_rows, q_rows, i
                                              axt_filter_host(...): the same on host threads
 pslFromAlign's column loop (psl.c:1716)      Engine.axt_psl(t_rows, q_rows)
                                              axt_psl_host(...): the same on host threads
+axtScoreSym, default scheme (axt.c:196)      Engine.axt_score(t_rows, q_rows)
+                                             axt_score_host(...): the same on host threads
 axtScoreUngapped per block (axt.c:186-194)   Engine.score_blocks / score_text_blocks (caller text)
 cBlockFindCrossover (chainConnect.c:61-105)  Engine.crossovers / text_crossovers (caller text)
 chainBlocks' kd-tree DP (chainBlock.c:400)   Engine.chain_dp_blocks (total, predecessor per block)
@@ -304,6 +306,18 @@ class Engine:
         check(lib().gac_axt_psl(self.h, len(ln), text, len(text), _p(t_off), _p(q_off), _p(ln),
                                 C.byref(res), C.byref(st)))
         return _axt_psl_result(res, st)
+
+    # ---- alignments to blastz scores (axtToMaf -score)
+    def axt_score(self, t_rows, q_rows):
+        """axtScoreDnaDefault of alignments' rows (gac_axt_score): t_rows and
+        q_rows as for axt_psl.  Returns (scores, stats): scores int32 [n],
+        stats: columns, host_entries, batches, fell_back."""
+        text, t_off, q_off, ln = _axt_psl_args(t_rows, q_rows, "axt_score")
+        score = np.zeros(len(ln), np.int32)
+        st = _lib.AxtScoreStats()
+        check(lib().gac_axt_score(self.h, len(ln), text, len(text), _p(t_off), _p(q_off), _p(ln),
+                                  _p(score), C.byref(st)))
+        return score, _axt_score_stats(st)
 
     # ---- alignment text (chainToAxt)
     @staticmethod
@@ -740,16 +754,16 @@ AXT_PSL_ENTRY = np.dtype([(name, {C.c_uint32: np.uint32, C.c_int32: np.int32, C.
                           for name, t in _lib.AxtPslEntry._fields_])
 
 
-def _axt_psl_args(t_rows, q_rows):
+def _axt_psl_args(t_rows, q_rows, who="axt_psl"):
     rows = [[r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in side]
             for side in (t_rows, q_rows)]
     if len(rows[0]) != len(rows[1]):
-        raise ValueError("axt_psl: as many target rows as query rows")
+        raise ValueError(who + ": as many target rows as query rows")
     n = len(rows[0])
     ln = np.fromiter((len(q) for q in rows[1]), np.int32, n)
     tl = np.fromiter((len(t) for t in rows[0]), np.int32, n)
     if np.any(tl != ln):
-        raise ValueError("axt_psl: a target row and its query row of different lengths")
+        raise ValueError(who + ": a target row and its query row of different lengths")
     # t0 q0 t1 q1 ...
     starts = np.concatenate([[0], np.cumsum(np.repeat(ln.astype(np.int64), 2))]).astype(np.int64)
     text = b"".join(x for pair in zip(rows[0], rows[1]) for x in pair)
@@ -783,6 +797,22 @@ def axt_psl_host(t_rows, q_rows, nthreads: int = 0):
     return _axt_psl_result(res, st)
 
 
+def _axt_score_stats(st):
+    return dict(columns=st.columns, host_entries=st.host_entries, batches=st.batches,
+                fell_back=st.fell_back)
+
+
+def axt_score_host(t_rows, q_rows, nthreads: int = 0):
+    """Engine.axt_score's result by one pass an entry on host threads
+    (gac_axt_score_host; no device): (scores, stats)."""
+    text, t_off, q_off, ln = _axt_psl_args(t_rows, q_rows, "axt_score")
+    score = np.zeros(len(ln), np.int32)
+    st = _lib.AxtScoreStats()
+    check(lib().gac_axt_score_host(len(ln), text, len(text), _p(t_off), _p(q_off), _p(ln), int(nthreads),
+                                   _p(score), C.byref(st)))
+    return score, _axt_score_stats(st)
+
+
 def antirepeat_pass(score: float, match, rep: int, total: int, min_score: int = 5000) -> bool:
     """chainAntiRepeat's keep/drop decision for one chain from its composition
     (gac_antirepeat_pass: degeneracyFilter then repeatFilter; host only)."""
@@ -804,4 +834,4 @@ def twobit_mask_runs(path: str, name: str) -> Tuple[np.ndarray, np.ndarray]:
 
 __all__ = ["Engine", "ChainSet", "GapCosts", "read_score_scheme", "GAC_T", "GAC_Q",
            "antirepeat_pass", "twobit_mask_runs", "depth_count_host", "prenet_keep_host",
-           "axt_filter_host", "axt_psl_host", "AXT_PSL_ENTRY"]
+           "axt_filter_host", "axt_psl_host", "AXT_PSL_ENTRY", "axt_score_host"]

@@ -47,6 +47,8 @@
  *                                                 src/filterAxtIdentityEntropy.py:32-69,88-110,144-162
  *   gac_axt_psl           <- trimAlignment + accumCounts + pslFromAlign's column loop
  *                                                 kent/src/lib/psl.c:1626-1806
+ *   gac_axt_score         <- axtScoreSym over axtScoreSchemeDefault (axtScoreDnaDefault)
+ *                                                 kent/src/lib/axt.c:196-229,291-298,423-458
  */
 #ifndef GACHAIN_H
 #define GACHAIN_H
@@ -69,8 +71,9 @@ extern "C" {
  * 5 = gac_depth_count and gac_depth_count_host (netSyntenic).
  * 6 = gac_prenet_keep and gac_prenet_keep_host (chainPreNet).
  * 7 = gac_axt_filter and gac_axt_filter_host (filterAxtIdentityEntropy.py).
- * 8 = gac_axt_psl, gac_axt_psl_host and gac_axtpsl_free (axtToPsl). */
-#define GAC_ABI_MINOR 8
+ * 8 = gac_axt_psl, gac_axt_psl_host and gac_axtpsl_free (axtToPsl).
+ * 9 = gac_axt_score and gac_axt_score_host (axtToMaf -score / -scoreZero). */
+#define GAC_ABI_MINOR 9
 
 /* return codes */
 #define GAC_OK 0
@@ -567,6 +570,54 @@ int gac_axt_psl_host(int64_t n, const char *text, int64_t text_bytes, const int6
                      gac_axtpsl_result **out, gac_axtpsl_stats *st);
 void gac_axtpsl_free(gac_axtpsl_result *r);
 
+/* ---- alignment text to blastz scores (axtToMaf -score / -scoreZero) --------
+ * score[i] is what axtScoreDnaDefault returns for entry i: axtScoreSym
+ * (kent/src/lib/axt.c:196-229) under axtScoreSchemeDefault (:423-458), over the
+ * entry's two rows of len[i] characters at text + t_off[i] and text + q_off[i]
+ * (given exactly as for gac_axt_filter and gac_axt_psl).
+ *
+ * A column is a gap column iff either character is '-' ('.', '=' and '_' are
+ * NOT gaps here, unlike in gac_axt_psl).  A gap column costs 30; one whose
+ * previous column is no gap column (column 0 included) costs 400 more.  A run
+ * of gap columns is one run whichever row holds the dash, columns with a dash
+ * in both rows included.  Any other column adds the blastz default matrix on
+ * its two letters, case-blind:
+ *            A     C     G     T
+ *      A    91  -114   -31  -123
+ *      C  -114   100  -125   -31
+ *      G   -31  -125   100  -114
+ *      T  -123   -31  -114    91
+ * and 0 if either character is outside acgtACGT ('N', 'n', '.', digits, bytes
+ * >= 0x80).  On bytes >= 0x80 the reference indexes its matrix with a negative
+ * char, which is undefined behaviour there; here such a byte scores 0.  The sum
+ * wraps as the reference's int does (two's complement, modulo 2^32).  len 0
+ * scores 0.  gac_set_scoring is neither needed nor read.
+ *
+ * A column's contribution depends on that column and the one before it only,
+ * so the device sums chunks of GAC_AXTSCORE_CHUNK columns independently
+ *  and the result is exact whatever the order.  The entries go
+ * in batches whose text stays under GAC_AXTSCORE_BATCH_BYTES (an environment
+ * knob; default as GAC_AXTF_BATCH_BYTES); an entry alone over that is scored
+ * by the host twin (fell_back 2).
+ *
+ * GAC_E_ARG: n < 0, a negative length or offset, a row reaching past
+ * text_bytes, a NULL array with n > 0.  n == 0 returns GAC_OK without a
+ * launch.  Host buffers, synchronous; needs no genomes.  st may be NULL. */
+#define GAC_AXTSCORE_CHUNK 1024
+typedef struct gac_axtscore_stats {
+    int64_t columns;            /* columns given */
+    int64_t host_entries;       /* entries scored by the host twin */
+    int32_t batches, fell_back; /* 0 device; 2 some entry over the byte budget (those entries on the host) */
+} gac_axtscore_stats;
+int gac_axt_score(gac_ctx *ctx, int64_t n, const char *text, int64_t text_bytes,
+                  const int64_t *t_off, const int64_t *q_off, const int32_t *len,
+                  int32_t *score, gac_axtscore_stats *st);
+/* The same scores by one pass an entry on nthreads host threads (<= 0:
+ * GAC_THREADS, else all CPUs); no device (axtToMaf -host, the fallback). */
+int gac_axt_score_host(int64_t n, const char *text, int64_t text_bytes, const int64_t *t_off,
+                       const int64_t *q_off, const int32_t *len, int nthreads,
+                       int32_t *score, gac_axtscore_stats *st);
+
 /* ---- alignment text (chainToAxt) ------------------------------------------
  * A piece is a window of consecutive blocks of one chain (gac_window: chain,
  * first_block, n_blocks; t_start / t_end are informative and not read) that
@@ -1032,7 +1083,8 @@ int gac_synchronize(gac_ctx *ctx);
 #define GAC_K_PRENET 4   /* gac_prenet_keep: every pass's fill, scans, mark and check (one lap per call) */
 #define GAC_K_AXTFILTER 5 /* gac_axt_filter: the window kernel (one lap per batch) */
 #define GAC_K_AXTPSL 6    /* gac_axt_psl: count, scan and emit (one lap per batch) */
-#define GAC_K_COUNT 7
+#define GAC_K_AXTSCORE 7  /* gac_axt_score: chunk counts, scan and the score kernel (one lap per batch) */
+#define GAC_K_COUNT 8
 #define GAC_PROF_ALL ((1 << GAC_K_COUNT) - 1)
 /* Event timing of each launch of the kernels in `mask` (bits 1 << GAC_K_*;
  * 0 = off, GAC_PROF_ALL = all).  Each timed kernel adds two event markers
