@@ -40,32 +40,60 @@
 typedef struct ngap ngap;
 typedef struct nfill nfill;
 
+/* A fill and its gaps are one group in a worker's arena: the 64-byte fill on
+ * a cache line of its own, then its n_gaps 32-byte gaps in block order.  A
+ * gap's parent fill is therefore found from the gap's own index (gap_parent),
+ * and a fill's gaps need no pointer array (fill_gap). */
+#define GAP_ROOT INT32_MIN /* ngap.pidx: a chromosome's root gap (no parent fill) */
+
 struct ngap {
     int start, end, o_start, o_end;
-    nfill *fill_head; /* slAddHead order until sorted */
-    nfill **fills;
-    int n_fills;
-    ngap *next;   /* in parent fill's list */
-    nfill *pfill; /* parent fill (NULL: a chromosome's root gap) */
-    int32_t pidx; /* index in pfill->gaps; for a root gap, the chromosome */
+    union {
+        nfill *fill_head; /* until sorted: slAddHead order (NULL: no fill) */
+        nfill **fills;    /* sorted, two or more fills */
+        nfill *one;       /* sorted, exactly one fill: the fill itself */
+    } u;
+    int32_t n_fills; /* 0 until sorted */
+    int32_t pidx;    /* index among its fill's gaps; a root gap: GAP_ROOT | chromosome */
 };
 
 struct nfill {
     int start, end, o_start, o_end;
     int32_t chain;
     int32_t ali;  /* the chain's aligned bases inside [start, end) (chainBaseCountSub*) */
-    ngap **gaps; /* ascending (created in block order at fill time) */
-    int n_gaps;
-    int32_t full; /* the final [start, end) covers the chain's header span on this side */
-    nfill *next;
+    int32_t n_gaps; /* the records right behind this one, ascending */
+    int32_t pidx;   /* index in its gap's fill list */
     int64_t ord;  /* pre-order index on its side */
-    ngap *pgap;   /* parent gap; index in pgap->fills; fills above this one */
-    int32_t pidx, level;
+    union {
+        nfill *next; /* in its gap's list, until the gap is sorted */
+        ngap *pgap;  /* parent gap, from then on */
+    } u;
     /* T side: the blocks chainSubsetOnT(chain, start, end) selects
      * (chain.c:481-500: from the first with tEnd > start while tStart < end),
      * chain-local first block and count, known from the netting's own walk */
     int32_t wb0, wn;
-};
+    /* level << 1 | full; full: the final [start, end) covers the chain's
+     * header span on this side; level: fills above this one (31 bits) */
+    uint32_t lvfull;
+    int32_t pad;
+} __attribute__((aligned(64)));
+
+_Static_assert(sizeof(nfill) == 64, "a fill is one cache line");
+_Static_assert(_Alignof(nfill) == 64, "a fill starts a cache line");
+_Static_assert(sizeof(ngap) == 32, "two gaps per cache line");
+_Static_assert(sizeof(nfill) % sizeof(ngap) == 0, "gaps follow their fill without padding");
+
+static inline ngap *fill_gap(const nfill *f, int i) { return (ngap *)(f + 1) + i; }
+static inline int32_t fill_level(const nfill *f) { return (int32_t)(f->lvfull >> 1); }
+static inline int fill_full(const nfill *f) { return (int)(f->lvfull & 1); }
+/* the fill a gap lies in (NULL: a chromosome's root gap) */
+static inline nfill *gap_parent(const ngap *g) {
+    return g->pidx < 0 ? NULL : (nfill *)((char *)(g - g->pidx) - sizeof(nfill));
+}
+/* a sorted gap's fills, ascending by start */
+static inline nfill *const *gap_fills(const ngap *g) {
+    return g->n_fills == 1 ? (nfill *const *)&g->u.one : (nfill *const *)g->u.fills;
+}
 
 typedef struct nchrom {
     const char *name;
@@ -80,6 +108,7 @@ typedef struct arena {
     char **blocks;
     size_t *sizes;
     size_t n, cap, used, bsize;
+    size_t block; /* block size (0: ARENA_BLOCK) */
 } arena;
 
 /* Arena blocks are 32 MB, 2 MB-aligned anonymous mappings advised for huge
@@ -88,7 +117,23 @@ typedef struct arena {
 #define ARENA_BLOCK ((size_t)32 << 20)
 #define ARENA_ALIGN ((size_t)2 << 20)
 
+/* The block size of a net's arenas: ARENA_BLOCK, or GAC_NET_ARENA_BLOCK bytes
+ * (tests only: blocks of a few records, so that groups roll over everywhere),
+ * a multiple of 64; read once per net, by gac_net_build */
+static size_t arena_block_size(void) {
+    const char *e = getenv("GAC_NET_ARENA_BLOCK");
+    return e && atoll(e) > 0 ? ((size_t)atoll(e) + 63) & ~(size_t)63 : ARENA_BLOCK;
+}
+
 static char *arena_map(size_t bs) {
+    if (bs < ARENA_ALIGN) { /* (a test's small block: plain pages) */
+        char *m = mmap(NULL, bs, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
+        if (m == MAP_FAILED) {
+            fprintf(stderr, "gac_net: out of memory mapping %zu bytes\n", bs);
+            abort();
+        }
+        return m;
+    }
     size_t len = bs + ARENA_ALIGN;
     char *m = mmap(NULL, len, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS, -1, 0);
     if (m == MAP_FAILED) {
@@ -106,20 +151,27 @@ static char *arena_map(size_t bs) {
     return p;
 }
 
+/* a fresh block for an allocation of sz bytes (one of its own, the oversize
+ * path, when sz is more than a block) */
+static void arena_grow(arena *a, size_t sz) {
+    if (a->n == a->cap) {
+        a->cap = a->cap ? a->cap * 2 : 64;
+        a->blocks = realloc(a->blocks, a->cap * sizeof(char *));
+        a->sizes = realloc(a->sizes, a->cap * sizeof(size_t));
+    }
+    const size_t block = a->block ? a->block : ARENA_BLOCK;
+    const size_t q = block < ARENA_ALIGN ? block : ARENA_ALIGN;
+    const size_t bs = sz > block ? (sz + q - 1) / q * q : block;
+    a->blocks[a->n] = arena_map(bs);
+    a->sizes[a->n++] = bs;
+    a->bsize = bs;
+    a->used = 0;
+}
+
 static void *arena_alloc(arena *a, size_t sz) {
     sz = (sz + 15) & ~(size_t)15;
-    if (a->n == 0 || a->used + sz > a->bsize) {
-        if (a->n == a->cap) {
-            a->cap = a->cap ? a->cap * 2 : 64;
-            a->blocks = realloc(a->blocks, a->cap * sizeof(char *));
-            a->sizes = realloc(a->sizes, a->cap * sizeof(size_t));
-        }
-        size_t bs = sz > ARENA_BLOCK ? (sz + ARENA_ALIGN - 1) & ~(ARENA_ALIGN - 1) : ARENA_BLOCK;
-        a->blocks[a->n] = arena_map(bs);
-        a->sizes[a->n++] = bs;
-        a->bsize = bs;
-        a->used = 0;
-    }
+    if (a->n == 0 || a->used + sz > a->bsize)
+        arena_grow(a, sz);
     char *p = a->blocks[a->n - 1] + a->used;
     a->used += sz;
     /* the next allocations land just past this one: fetch those lines for
@@ -127,6 +179,28 @@ static void *arena_alloc(arena *a, size_t sz) {
     if (a->used + 512 <= a->bsize)
         __builtin_prefetch(p + sz + 384, 1, 3);
     return p;
+}
+
+/* A fill's group: room for the fill and up to max_gaps gaps in one block, on
+ * a cache line boundary, not yet taken; arena_commit takes what was used.
+ * Nothing else is allocated from the arena in between. */
+static nfill *arena_reserve_group(arena *a, int max_gaps) {
+    const size_t sz = sizeof(nfill) + (size_t)max_gaps * sizeof(ngap);
+    size_t u = (a->used + 63) & ~(size_t)63;
+    if (a->n == 0 || u + sz > a->bsize) {
+        arena_grow(a, sz);
+        u = 0;
+    }
+    a->used = u;
+    return (nfill *)(a->blocks[a->n - 1] + u);
+}
+
+static void arena_commit_group(arena *a, int n_gaps) {
+    const size_t sz = (sizeof(nfill) + (size_t)n_gaps * sizeof(ngap) + 63) & ~(size_t)63;
+    char *p = a->blocks[a->n - 1] + a->used;
+    a->used += sz;
+    if (a->used + 512 <= a->bsize)
+        __builtin_prefetch(p + sz + 384, 1, 3);
 }
 
 /* The arenas' pages are dropped by madvise (under the mm's read lock, so the
@@ -165,6 +239,7 @@ typedef struct nwork {
     /* finishNet scratch: a gap's fill list gathered in one walk */
     struct nfill **sf;
     int64_t sf_cap;
+    int64_t n_fill, n_gap; /* records made (GAC_TIMING) */
     char pad[64]; /* keep workers' hot fields on separate cache lines */
 } nwork;
 
@@ -626,12 +701,16 @@ static void sp_replace(nwork *w, nchrom *c, int sstart, int send, const sitem *i
     free(nc);
 }
 
-static ngap *gap_new(nwork *n, int s, int e, int os, int oe) {
+/* a chromosome's root gap (every other gap is made in its fill's group).
+ * Fresh arena memory is zero: no fill, not sorted. */
+static ngap *root_gap_new(nwork *n, int size, int32_t chrom) {
     ngap *g = arena_alloc(&n->ar, sizeof(ngap));
-    g->start = s;
-    g->end = e;
-    g->o_start = os;
-    g->o_end = oe;
+    g->start = 0;
+    g->end = size;
+    g->o_start = 0;
+    g->o_end = 0;
+    g->pidx = GAP_ROOT | chrom;
+    ++n->n_gap;
     return g;
 }
 
@@ -663,7 +742,7 @@ static void add_chain_side(const gac_net *net, nwork *n, nchrom *c, int32_t chai
     /* each filled space's gap gets the fill pushed: its line is a cache
      * miss (the gap was made long before), so fetch them all now */
     for (int64_t si = 0; si < nsp; ++si)
-        __builtin_prefetch(&n->q[si].gap->fill_head, 1);
+        __builtin_prefetch(&n->q[si].gap->u.fill_head, 1);
     int k = 0;
     for (int64_t si = 0; si < nsp; ++si) {
         const int sstart = n->q[si].start, send = n->q[si].end;
@@ -705,10 +784,11 @@ static void add_chain_side(const gac_net *net, nwork *n, nchrom *c, int32_t chai
         }
         if (end < 0 || end - start < net->opt.min_fill)
             continue;
-        /* fillSpace (chainNet.c:487-523) */
-        nfill *f = arena_alloc(&n->ar, sizeof(nfill));
-        f->start = start;
-        f->end = end;
+        /* fillSpace (chainNet.c:487-523).  The fill and its gaps are one
+         * group: a gap strictly inside the space lies between two of the
+         * blocks the walk above saw, so there are fewer gaps than blocks seen */
+        const int max_gaps = wlast - wfirst;
+        nfill *f = arena_reserve_group(&n->ar, max_gaps);
         f->chain = chain;
         f->ali = (int32_t)ali;
         /* rCalcOtherFill (chainNet.c:393-484) now, on the same block slice:
@@ -717,7 +797,7 @@ static void add_chain_side(const gac_net *net, nwork *n, nchrom *c, int32_t chai
          * is unchanged, their spaces being disjoint) and the other side's
          * range (inv: the query side of a '-' chain, where the target runs
          * backwards; oflip: the target side of a '-' chain, whose query
-         * range is flipped to + strand coordinates); f->full is subchainInfo's
+         * range is flipped to + strand coordinates); the full bit is subchainInfo's
          * whole-chain test (chainNet.c:802-823) */
         /* Every block with bases in the space is inside [start, end), so
          * the loop above already clipped it the same way and saw it; only a
@@ -750,7 +830,7 @@ static void add_chain_side(const gac_net *net, nwork *n, nchrom *c, int32_t chai
             f->end = fe;
             f->o_start = omin;
             f->o_end = omax;
-            f->full = fs <= cstart && fe >= cend;
+            f->lvfull = fs <= cstart && fe >= cend; /* (the level comes with the sort) */
         }
         if (boff >= 0) {
             /* chainSubsetOnT's window of [fs, fe): every block the walk saw
@@ -771,27 +851,40 @@ static void add_chain_side(const gac_net *net, nwork *n, nchrom *c, int32_t chai
         /* slAddHead onto the space's gap; region workers of one chromosome
          * side (net_regions) may share the gap, so the push is atomic.  The
          * order does not matter: finishNet sorts a gap's fills by start. */
-        nfill *h = __atomic_load_n(&sgap->fill_head, __ATOMIC_RELAXED);
+        nfill *h = __atomic_load_n(&sgap->u.fill_head, __ATOMIC_RELAXED);
         do
-            f->next = h;
-        while (!__atomic_compare_exchange_n(&sgap->fill_head, &h, f, 1, __ATOMIC_RELEASE,
+            f->u.next = h;
+        while (!__atomic_compare_exchange_n(&sgap->u.fill_head, &h, f, 1, __ATOMIC_RELEASE,
                                             __ATOMIC_RELAXED));
         n->it_n = 0;
         if (start - sstart >= net->opt.min_space)
             it_push(n, sstart, start, sgap);
         /* gaps strictly inside the space (all inside [start, end]) */
-        const int64_t g0 = n->it_n;
+        int ng = 0;
         for (int b = k; b + 1 < nb; ++b) {
             int gs = e[b], ge = s[b + 1];
             if (ge >= send)
                 break;
-            if (strictly_inside(net, sstart, send, gs, ge))
-                it_push(n, gs, ge, gap_new(n, gs, ge, gos[b], goe[b]));
+            if (strictly_inside(net, sstart, send, gs, ge)) {
+                if (ng == max_gaps) { /* (cannot happen: see max_gaps) */
+                    fprintf(stderr, "gac_net: more gaps than a fill's group holds\n");
+                    abort();
+                }
+                /* the gap knows its place behind its fill now, while its
+                 * line is being written; the rest of it stays zero */
+                ngap *g = fill_gap(f, ng);
+                g->start = gs;
+                g->end = ge;
+                g->o_start = gos[b];
+                g->o_end = goe[b];
+                g->pidx = ng++;
+                it_push(n, gs, ge, g);
+            }
         }
-        f->n_gaps = (int)(n->it_n - g0);
-        f->gaps = f->n_gaps ? arena_alloc(&n->ar, f->n_gaps * sizeof(ngap *)) : NULL;
-        for (int i = 0; i < f->n_gaps; ++i)
-            f->gaps[i] = n->it[g0 + i].gap;
+        f->n_gaps = ng;
+        arena_commit_group(&n->ar, ng);
+        ++n->n_fill;
+        n->n_gap += ng;
         if (send - end >= net->opt.min_space)
             it_push(n, end, send, sgap);
         sp_replace(n, c, sstart, send, n->it, (int)n->it_n);
@@ -960,58 +1053,66 @@ static void finish_fill(fin_ctx *x, nfill *f) {
         x->ord = realloc(x->ord, (size_t)x->cap * sizeof(nfill *));
     }
     x->ord[x->n_ord++] = f;
-    for (int i = 0; i < f->n_gaps; ++i) {
-        f->gaps[i]->pfill = f;
-        f->gaps[i]->pidx = i;
-    }
     for (int i = 0; i < f->n_gaps; ++i)
-        finish_gap(x, f->gaps[i]);
+        finish_gap(x, fill_gap(f, i));
 }
 
+/* A gap's fill list into its sorted form (gap_fills): nothing for an empty
+ * gap (it is all zero already), the fill itself for one, an array for more.
+ * The list is walked to its end before the first fill's link is reused for
+ * its parent gap. */
 static void sort_gap_fills(nwork *w, ngap *g) {
-    if (!g->fill_head) {
-        g->n_fills = 0;
-        g->fills = NULL;
+    nfill *const head = g->u.fill_head;
+    if (!head)
+        return;
+    const nfill *const pf = gap_parent(g);
+    const uint32_t level2 = pf ? (uint32_t)(fill_level(pf) + 1) << 1 : 0;
+    if (!head->u.next) {
+        g->n_fills = 1; /* (u.one is the list's head) */
+        head->u.pgap = g;
+        head->pidx = 0;
+        head->lvfull = level2 | (head->lvfull & 1);
         return;
     }
     /* one walk of the list (its fills are scattered over the arenas: every
      * link is a miss) into the worker's scratch, then the exact array */
     int cnt = 0;
-    for (nfill *f = g->fill_head; f; f = f->next) {
+    for (nfill *f = head; f; f = f->u.next) {
         if (cnt == w->sf_cap) {
             w->sf_cap = w->sf_cap ? 2 * w->sf_cap : 4096;
             w->sf = realloc(w->sf, (size_t)w->sf_cap * sizeof(nfill *));
         }
         w->sf[cnt++] = f;
     }
+    nfill **fills = arena_alloc(&w->ar, cnt * sizeof(nfill *));
     g->n_fills = cnt;
-    g->fills = arena_alloc(&w->ar, cnt * sizeof(nfill *));
-    copy_fill(g->fills, w->sf, cnt);
-    const int32_t level = g->pfill ? g->pfill->level + 1 : 0;
+    g->u.fills = fills;
+    copy_fill(fills, w->sf, cnt);
     if (cnt <= 16) { /* fills of one gap are disjoint: starts are distinct */
         for (int i = 1; i < cnt; ++i) {
-            nfill *v = g->fills[i];
+            nfill *v = fills[i];
             int j = i - 1;
-            while (j >= 0 && g->fills[j]->start > v->start) {
-                g->fills[j + 1] = g->fills[j];
+            while (j >= 0 && fills[j]->start > v->start) {
+                fills[j + 1] = fills[j];
                 --j;
             }
-            g->fills[j + 1] = v;
+            fills[j + 1] = v;
         }
     } else {
-        qsort(g->fills, g->n_fills, sizeof(nfill *), cmp_fill);
+        qsort(fills, cnt, sizeof(nfill *), cmp_fill);
     }
     for (int i = 0; i < cnt; ++i) {
-        g->fills[i]->pgap = g;
-        g->fills[i]->pidx = i;
-        g->fills[i]->level = level;
+        fills[i]->u.pgap = g;
+        fills[i]->pidx = i;
+        fills[i]->lvfull = level2 | (fills[i]->lvfull & 1);
     }
 }
 
 static void finish_gap(fin_ctx *x, ngap *g) {
     sort_gap_fills(x->w, g);
+    nfill *const *fills = gap_fills(g);
     for (int i = 0; i < g->n_fills; ++i)
-        finish_fill(x, g->fills[i]);
+        finish_fill(x, fills[i]);
 }
 
 /* ------------------------------------------------------------ API */
@@ -1252,21 +1353,15 @@ static void sk_push(skel *k, nfill *f, ngap *g) {
 static void skel_fill(nwork *w, skel *k, nfill *f) {
     sk_push(k, f, NULL);
     for (int i = 0; i < f->n_gaps; ++i) {
-        f->gaps[i]->pfill = f;
-        f->gaps[i]->pidx = i;
-    }
-    for (int i = 0; i < f->n_gaps; ++i) {
-        ngap *g = f->gaps[i];
-        if (f->level < SKEL_DEPTH) {
+        ngap *g = fill_gap(f, i);
+        if (fill_level(f) < SKEL_DEPTH) {
             sort_gap_fills(w, g);
+            nfill *const *fills = gap_fills(g);
             for (int j = 0; j < g->n_fills; ++j)
-                skel_fill(w, k, g->fills[j]);
-        } else if (g->fill_head) {
+                skel_fill(w, k, fills[j]);
+        } else if (g->u.fill_head) {
             sk_push(k, NULL, g);
-        } else {
-            g->n_fills = 0;
-            g->fills = NULL;
-        }
+        } /* (an empty gap is left as it is: all zero) */
     }
 }
 
@@ -1330,8 +1425,9 @@ static void *fin_thread(void *arg) {
             if (!c->root)
                 continue;
             sort_gap_fills(w, c->root);
+            nfill *const *fills = gap_fills(c->root);
             for (int j = 0; j < c->root->n_fills; ++j)
-                skel_fill(w, &F->sk[k], c->root->fills[j]);
+                skel_fill(w, &F->sk[k], fills[j]);
         }
         return NULL;
     }
@@ -1672,8 +1768,7 @@ static double mono_s(void);
 static void big_prefix(gac_net *n, nwork *w, big_net *B, int nthreads) {
     net_task *t = B->t;
     nchrom *c = &n->chroms[t->side][t->chrom];
-    c->root = gap_new(w, 0, c->size, 0, 0);
-    c->root->pidx = t->chrom;
+    c->root = root_gap_new(w, c->size, t->chrom);
     sp_init(w, c, 0, c->size, c->root);
     const int32_t want = 4 * nthreads;
     int32_t *cuts = malloc((size_t)want * 4);
@@ -1786,8 +1881,7 @@ static void net_small(gac_net *n, nwork *w, const net_task *t) {
     nchrom *c = &n->chroms[t->side][t->chrom];
     /* makeChroms (chainNet.c:328-354): one gap = one space over the whole
      * sequence */
-    c->root = gap_new(w, 0, c->size, 0, 0);
-    c->root->pidx = t->chrom;
+    c->root = root_gap_new(w, c->size, t->chrom);
     sp_init(w, c, 0, c->size, c->root);
     net_chains(n, w, t->side, t->recs, t->n, c, INT32_MIN, INT32_MAX);
 }
@@ -2027,9 +2121,11 @@ static int net_build(const gac_net_input *in, const gac_net_opts *opt, int sides
     n->sides = sides;
     n->n_w = gac_host_threads();
     n->w = calloc((size_t)n->n_w, sizeof(nwork));
+    const size_t ablock = arena_block_size();
     for (int k = 0; k < n->n_w; ++k) {
         n->w[k].lf_free = -1;
         n->w[k].in_free = -1;
+        n->w[k].ar.block = ablock;
     }
     /* chains to net: in order until the first below minScore (must be
      * sorted), haplotype queries skipped unless incl_hap */
@@ -2222,7 +2318,7 @@ static int net_build(const gac_net_input *in, const gac_net_opts *opt, int sides
                     sk_item *it = &F.sk[k].it[i];
                     if (!it->g) {
                         SJ.sp[m++] = (ispan){&it->f, n->n_order[side], 1, side};
-                        if (it->f->level == 0)
+                        if (fill_level(it->f) == 0)
                             n->top[side][n->n_top[side]++] = n->n_order[side];
                         ++n->n_order[side];
                         continue;
@@ -2260,14 +2356,17 @@ static int net_build(const gac_net_input *in, const gac_net_opts *opt, int sides
     clock_gettime(CLOCK_MONOTONIC, &t_fin1);
     if (getenv("GAC_TIMING")) {
         size_t sp_bytes = 0, ar_bytes = 0;
+        long long fills = 0, gaps = 0;
         for (int i = 0; i < n->n_w; ++i) {
+            fills += n->w[i].n_fill;
+            gaps += n->w[i].n_gap;
             sp_bytes += (size_t)n->w[i].lf_cap * sizeof(sleaf) + (size_t)n->w[i].in_cap * sizeof(snode);
             for (size_t k = 0; k < n->w[i].ar.n; ++k)
                 ar_bytes += n->w[i].ar.sizes[k];
         }
-        fprintf(stderr, "[gac_net_build] finishNet %.3f s (space index %.0f MB, fill/gap arenas %.0f MB)\n",
+        fprintf(stderr, "[gac_net_build] finishNet %.3f s (space index %.0f MB, fill/gap arenas %.0f MB: %lld fills of %zu bytes, %lld gaps of %zu bytes)\n",
                 (t_fin1.tv_sec - t_fin0.tv_sec) + 1e-9 * (t_fin1.tv_nsec - t_fin0.tv_nsec),
-                sp_bytes / 1e6, ar_bytes / 1e6);
+                sp_bytes / 1e6, ar_bytes / 1e6, fills, sizeof(nfill), gaps, sizeof(ngap));
     }
     /* the space index is netting-only: released now, on a detached thread */
     space_release(n);
@@ -2327,7 +2426,7 @@ static void *fills_thread(void *arg) {
         for (int64_t i = a; i < b; ++i) {
             const nfill *f = n->order[side][i];
             const int64_t c = f->chain;
-            const int full = f->full;
+            const int full = fill_full(f);
             const int sz = full ? full_size(n, c) : f->ali;
             if (J->chain)
                 J->chain[i] = (int32_t)c;
@@ -2367,7 +2466,7 @@ static int64_t next_top_level(const gac_net *n, int side, int64_t i) {
             ++i;
         return i;
     }
-    while (i < n->n_order[side] && n->order[side][i]->pgap->pfill)
+    while (i < n->n_order[side] && gap_parent(n->order[side][i]->u.pgap))
         ++i;
     return i;
 }
@@ -2385,7 +2484,7 @@ static void *visible_thread(void *arg) {
         const int64_t b = next_top_level(n, side, (r + 1) * J->per < nf ? (r + 1) * J->per : nf);
         int64_t *po = J->po;
         for (int64_t i = a; i < b; ++i) {
-            const nfill *pf = n->order[side][i]->pgap->pfill;
+            const nfill *pf = gap_parent(n->order[side][i]->u.pgap);
             if (po)
                 po[i] = pf ? pf->ord : -1;
             const int sz = J->ali ? J->ali[i] : 0;
@@ -2496,13 +2595,13 @@ static void *rw_thread(void *arg) {
             if (i + 16 < b)
                 __builtin_prefetch(n->order[side][i + 16]);
             const nfill *f = n->order[side][i];
-            const nfill *pf = f->pgap->pfill;
+            const nfill *pf = gap_parent(f->u.pgap);
             if (J->po)
                 J->po[i] = pf ? pf->ord : -1;
-            const int sz = f->full ? full_size(n, f->chain) : f->ali;
+            const int sz = fill_full(f) ? full_size(n, f->chain) : f->ali;
             const uint8_t v = (!pf || J->vis[pf->ord]) && sz >= n->opt.min_fill;
             J->vis[i] = v;
-            if (!v || f->full)
+            if (!v || fill_full(f))
                 continue;
             if (R->n == R->cap) {
                 R->cap = R->cap ? 2 * R->cap : 4096;
@@ -2716,7 +2815,7 @@ static int fill_info(const gac_net *n, int side, const int64_t *tscore, const nf
     const int64_t c = f->chain;
     int sub;
     double score;
-    if (f->full) { /* the whole chain */
+    if (fill_full(f)) { /* the whole chain */
         score = in->score[c];
         sub = full_size(n, c);
     } else {
@@ -2741,7 +2840,7 @@ static void put_fill_line(const wctx *w, const nfill *f, int depth, double score
     const int64_t c = f->chain;
     const char *ochrom = w->side == GAC_Q ? in->t_names[in->t_seq[c]] : in->q_names[in->q_seq[c]];
     const int olen = w->side == GAC_Q ? w->n->nlen[GAC_T][in->t_seq[c]] : w->n->nlen[GAC_Q][in->q_seq[c]];
-    const int deferred = w->marks && w->side == GAC_T && !f->full;
+    const int deferred = w->marks && w->side == GAC_T && !fill_full(f);
     if (olen > 400 || depth > 400 || !(score > -1e300 && score < 1e300)) {
         gac_obuf_printf(w->o, "%*sfill %d %d %s %c %d %d id %d score ", depth, "", f->start,
                   f->end - f->start, ochrom, in->q_strand[c] ? '-' : '+', f->o_start,
@@ -2823,36 +2922,36 @@ typedef struct wjob {
 static int gap_prints_fill(const wjob *J, const ngap *g) {
     if (g->n_fills == 0)
         return 0;
-    const int64_t o = g->fills[0]->ord;
+    const int64_t o = gap_fills(g)[0]->ord;
     return J->show[o] || J->more[o];
 }
 
 static void write_segment(const wjob *J, wctx *w, int64_t i) {
     const nfill *f = J->ord[i];
-    if (!f->pgap->pfill && f->pidx == 0) { /* first top-level fill: the chromosome header */
-        const nchrom *c = &J->n->chroms[J->side][f->pgap->pidx];
+    if (f->u.pgap->pidx < 0 && f->pidx == 0) { /* first top-level fill: the chromosome header */
+        const nchrom *c = &J->n->chroms[J->side][f->u.pgap->pidx & INT32_MAX];
         gac_obuf_printf(w->o, "net %s %d\n", c->name, c->size);
     }
     if (!J->reached[i])
         return;
-    put_fill_line(w, f, 2 * f->level + 1, J->score[i], J->sub[i]);
+    put_fill_line(w, f, 2 * fill_level(f) + 1, J->score[i], J->sub[i]);
     const nfill *cur = f;
     int g0 = 0;
     for (;;) {
         for (int gi = g0; gi < cur->n_gaps; ++gi) {
-            const ngap *g = cur->gaps[gi];
-            put_gap_line(w, cur, g, 2 * cur->level + 2);
+            const ngap *g = fill_gap(cur, gi);
+            put_gap_line(w, cur, g, 2 * fill_level(cur) + 2);
             if (gap_prints_fill(J, g))
                 return; /* the next line is that fill's */
         }
         /* cur's subtree is done: its next printed sibling, or up */
         if (J->more[cur->ord])
             return;
-        const ngap *pg = cur->pgap;
-        if (!pg->pfill)
+        const ngap *pg = cur->u.pgap;
+        if (pg->pidx < 0)
             return; /* end of the chromosome */
         g0 = pg->pidx + 1;
-        cur = pg->pfill;
+        cur = gap_parent(pg);
     }
 }
 
@@ -2868,16 +2967,15 @@ static void write_run(gac_obuf *o, int64_t r, void *arg) {
             __builtin_prefetch(J->ord[i + 16]);
         if (i + 8 < b) {
             const nfill *f = J->ord[i + 8];
-            __builtin_prefetch(f->gaps);
             __builtin_prefetch(&in->q_seq[f->chain]);
             __builtin_prefetch(&in->q_strand[f->chain]);
             __builtin_prefetch(&in->id[f->chain]);
             __builtin_prefetch(&in->t_seq[f->chain]);
         }
-        if (i + 4 < b) {
+        if (i + 4 < b) { /* (its gaps lie right behind it, two to a line) */
             const nfill *f = J->ord[i + 4];
-            for (int k = 0; k < f->n_gaps && k < 4; ++k)
-                __builtin_prefetch(f->gaps[k]);
+            for (int k = 0; k < f->n_gaps && k < 4; k += 2)
+                __builtin_prefetch(fill_gap(f, k));
         }
         write_segment(J, &w, i);
     }
@@ -2901,7 +2999,7 @@ static void *winfo_thread(void *arg) {
             }
             J->show[i] = (uint8_t)fill_info(J->n, J->side, J->tscore, J->ord[i], &J->score[i],
                                             &J->sub[i]);
-            const int32_t L = J->ord[i]->level;
+            const int32_t L = fill_level(J->ord[i]);
             J->lvl[i] = (uint16_t)(L < 65535 ? L : 65535);
             J->pix[i] = J->ord[i]->pidx;
             if (L >= 65535)
@@ -2914,8 +3012,9 @@ static void *winfo_thread(void *arg) {
 /* "more" flags: every gap's fills, last to first */
 static void mark_more(wjob *J, const ngap *g) {
     uint8_t any = 0;
+    nfill *const *fills = gap_fills(g);
     for (int k = g->n_fills - 1; k >= 0; --k) {
-        const int64_t o = g->fills[k]->ord;
+        const int64_t o = fills[k]->ord;
         J->more[o] = any;
         any |= J->show[o];
     }
@@ -2933,12 +3032,12 @@ static void *wmore_thread(void *arg) {
                 __builtin_prefetch(J->ord[i + 16]);
             if (i + 8 < b) {
                 const nfill *p = J->ord[i + 8];
-                for (int k = 0; k < p->n_gaps && k < 4; ++k)
-                    __builtin_prefetch(p->gaps[k]);
+                for (int k = 0; k < p->n_gaps && k < 4; k += 2)
+                    __builtin_prefetch(fill_gap(p, k));
             }
             const nfill *f = J->ord[i];
             for (int k = 0; k < f->n_gaps; ++k)
-                mark_more(J, f->gaps[k]);
+                mark_more(J, fill_gap(f, k));
         }
     }
     return NULL;
@@ -3049,7 +3148,7 @@ static void *wreached_thread(void *arg) {
             continue;
         }
         for (int64_t i = a; i < b; ++i) {
-            const nfill *pf = J->ord[i]->pgap->pfill;
+            const nfill *pf = gap_parent(J->ord[i]->u.pgap);
             J->reached[i] = J->show[i] && (!pf || J->reached[pf->ord]);
         }
     }
@@ -3132,7 +3231,7 @@ static void wjob_flags(wjob *J, const gac_net *n, int side, const int64_t *tscor
     gac_mark("flags: more done");
     for (int32_t k = 0; k < n->n_chroms[side]; ++k) {
         const nchrom *c = &n->chroms[side][k];
-        if (c->root && c->root->fill_head)
+        if (c->root && c->root->n_fills)
             mark_more(J, c->root);
     }
     gac_mark("flags: roots done");

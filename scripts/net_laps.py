@@ -2,9 +2,10 @@
 """The netting stage of the headline tool (bin/chainNet -rescore on C5,
 bench.py's files) under variants, alternating, every run with GAC_TIMING:
 per rep the [stage] lines (netting: wall and CPU) and the [gac_net_build]
-laps (set-up, addChainT/Q, finishNet skeletons / subtrees / index), then the
-medians and, against the first variant, the reps in which the netting stage's
-wall and CPU were both lower.  scripts/c5_ab.py times the whole step; this
+laps (set-up, addChainT/Q, finishNet skeletons / subtrees / index, the arena
+MB) and the stages after it (fill list, write nets, free), then the medians
+and, against the first variant, the reps in which the netting stage's wall and
+CPU were both lower and, lap by lap, the pairs in which each was lower.  scripts/c5_ab.py times the whole step; this
 one attributes it.
 usage: net_laps.py REPS tag:ENV=v,@TOOL=path ...   (as c5_ab.py)"""
 import os
@@ -18,7 +19,10 @@ import bench  # noqa: E402
 LAPS = [("netting", r"\[stage\] netting\s+([\d.]+) s"), ("netting cpu", r"\[stage\] netting.*\(cpu ([\d.]+) s"),
         ("set-up", r"\] set-up ([\d.]+) s"), ("addChainT/Q", r"\] addChainT/Q ([\d.]+) s"),
         ("skeletons", r"finishNet skeletons ([\d.]+) s"), ("subtrees", r"subtrees ([\d.]+) s"),
-        ("index", r"index ([\d.]+) s")]
+        ("index", r"index ([\d.]+) s"), ("finishNet", r"\] finishNet ([\d.]+) s \("),
+        ("fill list", r"\[stage\] fill list\s+([\d.]+) s"), ("write nets", r"\[stage\] write nets\s+([\d.]+) s"),
+        ("free", r"\[stage\] free nets and chains\s+([\d.]+) s"),
+        ("arenas MB", r"fill/gap arenas ([\d.]+) MB")]
 
 
 def main():
@@ -69,6 +73,10 @@ def main():
                    b["netting cpu"][r] < a["netting cpu"][r]]
             print(f"== {tag}: netting stage and its CPU below {first}'s in {len(low)} of {reps} "
                   f"pairs (reps {' '.join(map(str, low))})", flush=True)
+            for k, _ in LAPS:  # each lap on its own: the pairs it was lower in
+                if len(a[k]) == reps and len(b[k]) == reps:
+                    print(f"== {tag}: {k} below {first}'s in "
+                          f"{sum(b[k][r] < a[k][r] for r in range(reps))} of {reps} pairs", flush=True)
 
 
 if __name__ == "__main__":
