@@ -36,10 +36,10 @@ EXECDIR  := $(PKG)/libexec
 # by blit kernels instead of the SDMA engines (HSA_ENABLE_SDMA=0: 20 vs 13
 # GB/s for the genome uploads on the box, profiles/r02f_*), and execs it --
 # before anything touches the GPU.  Either can be overridden from outside.
-# NetFilterNonNested.perl, chainSort, chainMergeSort, chainToPslBasic and
-# axtSort are host-only: in bin/.
-GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt netToAxt chainToPsl netSyntenic chainPreNet filterAxtIdentityEntropy.py axtToPsl axtToMaf
-HOST_TOOLS := NetFilterNonNested.perl chainSort chainMergeSort chainToPslBasic axtSort
+# NetFilterNonNested.perl, chainSort, chainMergeSort, chainToPslBasic,
+# axtSort and lavToPsl are host-only: in bin/.
+GPU_TOOLS := scoreChain chainNet chainCleaner axtChain chainAntiRepeat chainToAxt netToAxt chainToPsl netSyntenic chainPreNet filterAxtIdentityEntropy.py axtToPsl axtToMaf lavToAxt
+HOST_TOOLS := NetFilterNonNested.perl chainSort chainMergeSort chainToPslBasic axtSort lavToPsl
 TOOLS    := $(addprefix $(EXECDIR)/,$(GPU_TOOLS)) $(addprefix $(BINDIR)/,$(GPU_TOOLS)) \
             $(addprefix $(BINDIR)/,$(HOST_TOOLS))
 TOOL_LIB_SRC := $(wildcard $(CSRC)/tools/lib/*.c)
@@ -79,7 +79,7 @@ $(BINDIR)/NetFilterNonNested.perl: $(CSRC)/tools/NetFilterNonNested.perl.c $(TOO
 	$(CC) $(CFLAGS) -I$(CSRC)/tools/lib $< $(TOOL_LIB_OBJ) -o $@ -L$(LIBDIR) -lgachain \
 	    -Wl,-rpath,'$$ORIGIN/../lib' -lz -lm -lpthread
 
-$(BINDIR)/chainSort $(BINDIR)/chainMergeSort $(BINDIR)/chainToPslBasic $(BINDIR)/axtSort: $(BINDIR)/%: $(CSRC)/tools/%.c $(TOOL_LIB_OBJ) $(LIBDIR)/libgachain.so $(HDRS)
+$(BINDIR)/chainSort $(BINDIR)/chainMergeSort $(BINDIR)/chainToPslBasic $(BINDIR)/axtSort $(BINDIR)/lavToPsl: $(BINDIR)/%: $(CSRC)/tools/%.c $(TOOL_LIB_OBJ) $(LIBDIR)/libgachain.so $(HDRS)
 	@mkdir -p $(BINDIR)
 	$(CC) $(CFLAGS) -I$(CSRC)/tools/lib $< $(TOOL_LIB_OBJ) -o $@ -L$(LIBDIR) -lgachain \
 	    -Wl,-rpath,'$$ORIGIN/../lib' -lz -lm -lpthread

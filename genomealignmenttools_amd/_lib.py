@@ -245,6 +245,13 @@ _PROTOS = {
     "gac_axt_measure_device": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                   C.c_void_p, C.c_void_p]),
+    "gac_axt_pair_counts": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "gac_axt_pair_counts_device": (
+        C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gac_axt_pair_counts_host": (
+        C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(ChainsetDesc), C.c_void_p, C.c_int64, C.c_void_p,
+                  C.c_void_p]),
     "gac_axt_render": (
         C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
     "gac_axt_render_device": (

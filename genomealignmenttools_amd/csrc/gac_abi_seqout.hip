@@ -420,6 +420,56 @@ extern "C" int gac_axt_measure_clip(gac_ctx *c, const gac_chainset *cs, const ga
     return axt_measure_x(c, cs, pieces, n, score, match, ali, sym, true);
 }
 
+// Letter-pair counts (lavToAxt -dropSelf): the plan step of measure, then
+// k_axt_pairs adding into the zeroed result arrays.
+static int axt_pairs_dev(gac_ctx *c, const gac_chainset *cs, AxtWs &ws, const gac_window *h_pieces,
+                         const gac_window *d_pieces, int64_t n, int64_t *d_pairs, int64_t *d_ncols,
+                         bool own_out, hipStream_t s) {
+    AxtPairArgs a;
+    int rc = axt_plan(c, cs, ws, h_pieces, d_pieces, n, false, s, a);
+    if (rc != GAC_OK) return rc;
+    if (own_out) {  // the host entry point's results: pairs, then ncols
+        HIPCHK(arena_need(ws.a2, (size_t)n * 17 * 8, s));
+        d_pairs = (int64_t *)ws.a2.p;
+        d_ncols = d_pairs + n * 16;
+    }
+    a.pairs = (unsigned long long *)d_pairs;
+    a.ncols = (unsigned long long *)d_ncols;
+    HIPCHK(hipMemsetAsync(d_pairs, 0, (size_t)n * 16 * 8, s));
+    HIPCHK(hipMemsetAsync(d_ncols, 0, (size_t)n * 8, s));
+    HIPCHK(launch_axt_pairs(a, s));
+    int32_t st = 0;
+    rc = axt_status(ws, a, s, &st);
+    if (rc != GAC_OK) return rc;
+    if (st & kAxtBadGap) return axt_bad_gap();
+    return GAC_OK;
+}
+
+extern "C" int gac_axt_pair_counts_device(gac_ctx *c, const gac_chainset *cs,
+                                          const gac_window *d_pieces, int64_t n, int64_t *d_pairs,
+                                          int64_t *d_n_cols, void *stream) {
+    AXT_ENTRY(c, cs);
+    if (n == 0) return GAC_OK;
+    if (n > 0 && (!d_pieces || !d_pairs || !d_n_cols)) return gac_fail(GAC_E_ARG, "NULL buffer");
+    return axt_pairs_dev(c, cs, *c->axt, nullptr, d_pieces, n, d_pairs, d_n_cols, false,
+                         stream ? (hipStream_t)stream : c->stream);
+}
+
+extern "C" int gac_axt_pair_counts(gac_ctx *c, const gac_chainset *cs, const gac_window *pieces,
+                                   int64_t n, int64_t *pairs, int64_t *n_cols) {
+    AXT_ENTRY(c, cs);
+    if (n == 0) return GAC_OK;
+    if (n > 0 && (!pieces || !pairs || !n_cols)) return gac_fail(GAC_E_ARG, "NULL buffer");
+    hipStream_t s = c->stream;
+    int rc = axt_pairs_dev(c, cs, *c->axt, pieces, nullptr, n, nullptr, nullptr, true, s);
+    if (rc != GAC_OK) return rc;
+    const int64_t *p = (const int64_t *)c->axt->a2.p;
+    HIPCHK(hipMemcpyAsync(pairs, p, (size_t)n * 16 * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_cols, p + n * 16, (size_t)n * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return GAC_OK;
+}
+
 extern "C" int gac_axt_render_device(gac_ctx *c, const gac_chainset *cs, const gac_window *d_pieces,
                                      int64_t n, const int64_t *d_offsets, char *d_out,
                                      int64_t out_bytes, void *stream) {

@@ -17,6 +17,8 @@
 //                 sequence and are added once per block.  Per-piece sums go
 //                 registers -> wave shuffles or LDS slots -> one global
 //                 atomicAdd per workgroup, piece and counter.
+//   k_axt_pairs   k_axt_stat's walk for any score scheme (lavToAxt -dropSelf):
+//                 per piece the 16 letter-pair counts and the N columns.
 //   k_axt_render  a block's run on a row is its inner gap's columns followed
 //                 by its bases; the run's first column is S[v] - S[first v of
 //                 the piece], S = exclusive scan of gap + size over the
@@ -388,6 +390,157 @@ __global__ void __launch_bounds__(256) k_axt_fin(AxtArgs a) {
     a.sym[i] = (int64_t)s[3];
 }
 
+// ------------------------------------------------------------------ pairs
+// k_axt_pairs (gac_axt_pair_counts): k_axt_stat's walk with the letters kept
+// apart.  Per 32-column chunk, four masks of the target code and four of the
+// query code give the 16 (query, target) letter masks; their popcounts under
+// `ok` and the popcount of the columns with an N are the lane's 17 counters.
+// A lane adds at most 32 to a counter per chunk and walks fewer than 2^24
+// chunks of a tile (64 blocks below 2^29 bases over 64 lanes), so 32-bit lane
+// registers hold; a wave's and a workgroup's sums do not (256 blocks of 2^29
+// bases), so the LDS slots and the global counters are 64 bits wide.
+constexpr int kPairVals = 17;  // [0, 16): q * 4 + t in A, C, G, T order; [16]: N columns
+
+// .2bit code (T=0 C=1 A=2 G=3) to the A, C, G, T index of gac_scheme_read
+__device__ __forceinline__ constexpr int pair_acgt(int code) {
+    return code == 0 ? 3 : code == 1 ? 1 : code == 2 ? 0 : 2;
+}
+
+// As stat_flush: the lanes' register sums to the piece slots.
+__device__ __forceinline__ void pair_flush(unsigned long long (*acc)[kPairVals], int lane, int &cur,
+                                           uint32_t (&v)[kPairVals], bool want) {
+    const bool have = cur >= 0;
+    if (!__ballot(want && have)) return;
+    const unsigned long long hm = __ballot(have);
+    const int u = __shfl(cur, (int)__builtin_ctzll(hm), kWave);
+    if (!__ballot(have && cur != u)) {
+#pragma unroll
+        for (int k = 0; k < kPairVals; ++k) {
+            unsigned long long s = have ? (unsigned long long)v[k] : 0ull;
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, kWave);
+            if (lane == 0 && s) atomicAdd(&acc[u][k], s);
+            v[k] = 0;
+        }
+        cur = -1;
+    } else if (want && have) {
+#pragma unroll
+        for (int k = 0; k < kPairVals; ++k) {
+            if (v[k]) atomicAdd(&acc[cur][k], (unsigned long long)v[k]);
+            v[k] = 0;
+        }
+        cur = -1;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_axt_pairs(AxtPairArgs a) {
+    __shared__ StatWave s_w[kWavesPerWG];
+    __shared__ unsigned long long s_acc[kAxtSlots][kPairVals];
+    __shared__ long long s_piece[kAxtSlots];
+#pragma unroll
+    for (int k = 0; k < kPairVals; ++k) s_acc[threadIdx.x][k] = 0ull;
+    s_piece[threadIdx.x] = -1;
+    __syncthreads();
+    const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+    const int64_t V0 = (int64_t)blockIdx.x * kAxtSlots;
+    const int64_t tile = (int64_t)blockIdx.x * kWavesPerWG + wv;
+    if (tile * kTileBlocks < a.V) {  // (wave-uniform; no workgroup barrier inside)
+        StatWave &W = s_w[wv];
+        const int64_t v = tile * kTileBlocks + lane;
+        int len = 0, lenq = 0, slot = 0;
+        long long tpos = 0, qpos = 0;
+        if (v < a.V) {
+            const AxtLoc L = axt_locate<false>(a, v);
+            if (L.bad) atomicOr(a.status, kAxtBadGap);
+            len = L.size;
+            const bool minus = L.ch.qbase < 0;
+            tpos = L.ch.tbase + L.bk.x;
+            qpos = minus ? ~L.ch.qbase - L.bk.y : L.ch.qbase + L.bk.y;
+            lenq = len | (minus ? (int)0x80000000 : 0) | (L.bk.z & (kTHasN | kQHasN));
+            slot = (int)((L.v0 > V0 ? L.v0 : V0) - V0);
+            s_piece[slot] = L.p;  // (every block of the piece writes the same value)
+        }
+        const int nch = (len + 31) >> 5;
+        int incl = nch;
+#pragma unroll
+        for (int d = 1; d < kWave; d <<= 1) {
+            const int o = __shfl_up(incl, d, kWave);
+            if (lane >= d) incl += o;
+        }
+        const int C = __shfl(incl, kWave - 1, kWave);
+        W.coff[lane] = incl - nch;  // (lanes past the last block hold C)
+        W.tpos[lane] = tpos;
+        W.qpos[lane] = qpos;
+        W.lenq[lane] = lenq;
+        W.slot[lane] = slot;
+        axt_wave_sync();
+
+        int cur = -1;
+        uint32_t acc[kPairVals];
+#pragma unroll
+        for (int k = 0; k < kPairVals; ++k) acc[k] = 0;
+        for (int c0 = 0; c0 < C; c0 += kWave) {
+            const int j = c0 + lane;
+            const bool on = j < C;
+            int k = 0;
+            if (on) {  // block owning chunk j: the largest k with coff[k] <= j
+#pragma unroll
+                for (int step = 32; step > 0; step >>= 1)
+                    if (W.coff[k + step] <= j) k += step;
+            }
+            const int sl = on ? W.slot[k] : -1;
+            pair_flush(s_acc, lane, cur, acc, on && sl != cur);
+            if (on) {
+                const int lq = W.lenq[k];
+                const int off = (j - W.coff[k]) << 5;
+                const int n = min(32, (lq & kSizeMask) - off);  // >= 1: chunk j exists
+                const bool minus = lq < 0;
+                const int sh = 32 - n;
+                const int64_t tp = W.tpos[k] + off;
+                // '-': the forward window that ends where the chunk starts
+                const int64_t qp = minus ? W.qpos[k] - off - n : W.qpos[k] + off;
+                const int64_t tw = tp >> 5, qw = qp >> 5;
+                const int sht = (int)(tp & 31), shq = (int)(qp & 31);
+                const au32x4a8 tv = *reinterpret_cast<const au32x4a8 *>(a.t_planes + tw);
+                const au32x4a8 qv = *reinterpret_cast<const au32x4a8 *>(a.q_planes + qw);
+                uint32_t nm = 0, qn = 0;
+                if (lq & kTHasN) nm = amask_window(a.t_nmask, tw, sht);
+                if (lq & kQHasN) qn = amask_window(a.q_nmask, qw, shq);
+                const uint32_t t0 = afunnel(tv.z, tv.x, sht), t1 = afunnel(tv.w, tv.y, sht);
+                uint32_t q0 = afunnel(qv.z, qv.x, shq), q1 = afunnel(qv.w, qv.y, shq);
+                if (minus) {
+                    q0 = __builtin_bitreverse32(q0) >> sh;
+                    q1 = ~(__builtin_bitreverse32(q1) >> sh);
+                    qn = __builtin_bitreverse32(qn) >> sh;
+                }
+                const uint32_t in = n >= 32 ? 0xffffffffu : ((1u << n) - 1u);
+                const uint32_t ok = in & ~(nm | qn);
+                // by code T=0 C=1 A=2 G=3 (bit 0: plane 0, bit 1: plane 1)
+                const uint32_t tm[4] = {~t0 & ~t1 & ok, t0 & ~t1 & ok, ~t0 & t1 & ok, t0 & t1 & ok};
+                const uint32_t qm[4] = {~q0 & ~q1, q0 & ~q1, ~q0 & q1, q0 & q1};
+#pragma unroll
+                for (int qc = 0; qc < 4; ++qc)
+#pragma unroll
+                    for (int tc = 0; tc < 4; ++tc)
+                        acc[pair_acgt(qc) * 4 + pair_acgt(tc)] +=
+                            (uint32_t)__builtin_popcount(qm[qc] & tm[tc]);
+                acc[16] += (uint32_t)__builtin_popcount((nm | qn) & in);
+                cur = sl;
+            }
+        }
+        pair_flush(s_acc, lane, cur, acc, true);
+    }
+    __syncthreads();
+    const long long p = s_piece[threadIdx.x];
+    if (p >= 0) {  // one add per (workgroup, piece, counter)
+        const unsigned long long *s = s_acc[threadIdx.x];
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (s[k]) atomicAdd(&a.pairs[p * 16 + k], s[k]);
+        if (s[16]) atomicAdd(&a.ncols[p], s[16]);
+    }
+}
+
 // ---------------------------------------------------------------- columns
 // S[v] = columns of virtual block v (inner gap + size), scanned afterwards.
 template <bool kClip>
@@ -729,6 +882,14 @@ hipError_t launch_axt_stat(const AxtArgs &a, hipStream_t s) {
         hipLaunchKernelGGL(a.clip ? k_axt_stat<true> : k_axt_stat<false>,
                            dim3((unsigned)((a.V + kAxtSlots - 1) / kAxtSlots)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_axt_fin, dim3(grid256(a.n)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// pairs and ncols (zeroed by the caller) take the workgroups' sums as they are
+hipError_t launch_axt_pairs(const AxtPairArgs &a, hipStream_t s) {
+    if (a.n <= 0 || a.V <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_axt_pairs, dim3((unsigned)((a.V + kAxtSlots - 1) / kAxtSlots)), dim3(256), 0, s,
+                       a);
     return hipGetLastError();
 }
 

@@ -332,6 +332,13 @@ struct AxtArgs {
     int64_t out_bytes;
 };
 
+// k_axt_pairs (gac_axtout.hip): the plan fields of AxtArgs and the two result
+// arrays, which the workgroups add into directly
+struct AxtPairArgs : AxtArgs {
+    unsigned long long *pairs;  // [n][16] q * 4 + t, A,C,G,T order (zeroed by the caller)
+    unsigned long long *ncols;  // [n] columns with an N on either side (zeroed by the caller)
+};
+
 // k_cut_* (gac_axtout.hip): ranges (chain, tStart, tEnd) to the clipped pieces
 // chainToAxt(chainSubsetOnT(...)) makes.  The ranges' selected blocks laid end
 // to end are the call's virtual blocks: rboff[r] = first of range r.
@@ -410,6 +417,7 @@ hipError_t launch_psl_counts(const PslArgs &a, hipStream_t s);
 // ---- gac_axtout.hip
 hipError_t launch_axt_plan(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_stat(const AxtArgs &a, hipStream_t s);
+hipError_t launch_axt_pairs(const AxtPairArgs &a, hipStream_t s);
 hipError_t launch_axt_place(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_render(const AxtArgs &a, hipStream_t s);
 hipError_t launch_axt_cut_find(const AxtCutArgs &a, hipStream_t s);

@@ -514,8 +514,19 @@ int gac_scheme_read(const char *path, int32_t mat[16], int32_t *gap_open,
     memcpy(text, m.data, m.size);
     text[m.size] = 0;
     gac_unmap_file(&m);
+    char *cur = text;
+    int line = 0;
+    rc = gac_scheme_parse(&cur, &line, path, mat, gap_open, gap_extend, extra);
+    free(text);
+    return rc;
+}
 
-    sc_lines l = {text, 0};
+int gac_scheme_parse(char **cur, int *line_no, const char *path, int32_t mat[16],
+                     int32_t *gap_open, int32_t *gap_extend, char **extra) {
+    int rc;
+    if (extra)
+        *extra = NULL;
+    sc_lines l = {*cur, *line_no};
     char *row[6];
     char *ex = calloc(1, 64);
     size_t exlen = 0, excap = 64;
@@ -618,7 +629,8 @@ int gac_scheme_read(const char *path, int32_t mat[16], int32_t *gap_open,
     rc = GAC_OK;
 out:
     free(ex);
-    free(text);
+    *cur = l.cur;
+    *line_no = l.line;
     return rc;
 }
 

@@ -37,6 +37,13 @@ int gac_chop_white(char *s, char **words, int max);
 /* Case-insensitive string equality (kent sameWord). */
 int gac_same_word(const char *a, const char *b);
 
+/* gac_scheme_read's parser (axtScoreSchemeReadLf) on text in memory: reads
+ * lines from *cur (NUL-terminated; cut in place) and leaves *cur after the
+ * last line it consumed, *line_no counting them (the lav reader's d stanza).
+ * path is only named in the messages. */
+int gac_scheme_parse(char **cur, int *line_no, const char *path, int32_t mat[16],
+                     int32_t *gap_open, int32_t *gap_extend, char **extra);
+
 /* ---- 2bit index (kent/src/lib/twoBit.c:420-635) ---- */
 typedef struct gac_twobit_seq {
     char *name;
@@ -176,6 +183,12 @@ gac_axtpsl_result *gac_axtpsl_alloc(int64_t n, int64_t n_blocks);
 /* gac_axt_score's argument check (shared with gac_axt_score_host) */
 int gac_axtscore_check(int64_t n, const char *text, int64_t text_bytes, const int64_t *t_off,
                        const int64_t *q_off, const int32_t *len, const int32_t *score);
+
+/* gac_axt_pair_counts_host on two opened files (t_seq / q_seq number their
+ * sequences in file order) */
+int gac_axt_pair_counts_twobit(const gac_twobit *t, const gac_twobit *q, const gac_chainset_desc *d,
+                               const gac_window *pieces, int64_t n, int64_t *pairs,
+                               int64_t *n_cols);
 
 /* ---- host view of a resident sequence (kept after gac_genome_finalize) ----
  * packed: 2 bits/base MSB-first (T=0 C=1 A=2 G=3); N runs merged and sorted. */

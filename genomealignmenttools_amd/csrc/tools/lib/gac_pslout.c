@@ -26,16 +26,21 @@ static char *put_list(FILE *f, char *buf, size_t cap, char *p, const int32_t *v,
 }
 
 void gt_write_psl(FILE *f, const gt_chains *c, int64_t i, const int64_t counts[4], int basic) {
+    gt_write_psl_ex(f, c, i, counts, basic, !basic, 0);
+}
+
+void gt_write_psl_ex(FILE *f, const gt_chains *c, int64_t i, const int64_t counts[4], int basic,
+                     int ins_ne, char t_strand) {
     const int64_t b0 = c->blk_off[i], nb = c->blk_off[i + 1] - b0;
     const int32_t *bt = c->bt + b0, *bq = c->bq + b0, *bs = c->bs + b0;
     uint32_t qn = 0, qb = 0, tn = 0, tb = 0; /* the reference's ints: 32-bit sums */
     for (int64_t b = 0; b + 1 < nb; ++b) {
         const int32_t dq = bq[b + 1] - (bq[b] + bs[b]), dt = bt[b + 1] - (bt[b] + bs[b]);
-        if (basic ? dq > 0 : dq != 0) {
+        if (ins_ne ? dq != 0 : dq > 0) {
             ++qn;
             qb += (uint32_t)dq;
         }
-        if (basic ? dt > 0 : dt != 0) {
+        if (ins_ne ? dt != 0 : dt > 0) {
             ++tn;
             tb += (uint32_t)dt;
         }
@@ -53,6 +58,8 @@ void gt_write_psl(FILE *f, const gt_chains *c, int64_t i, const int64_t counts[4
     p = put(p, tn, basic, '\t');
     p = put(p, tb, 0, '\t');
     *p++ = c->qstrand[i] ? '-' : '+';
+    if (t_strand)
+        *p++ = t_strand;
     *p++ = '\t';
     memcpy(p, qname, ql);
     p += ql;

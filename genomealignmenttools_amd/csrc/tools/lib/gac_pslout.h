@@ -20,6 +20,11 @@ extern "C" {
  * every number "%d".  For '-' qStart / qEnd are flipped with the header's
  * qSize; qStarts are the chain's own strand coordinates. */
 void gt_write_psl(FILE *f, const gt_chains *c, int64_t i, const int64_t counts[4], int basic);
+/* The same with the two rules apart (lavToPsl prints as pslTabOut does, basic,
+ * but counts an insert wherever two blocks do not abut, ins_ne), and with a
+ * target strand character after the query's (0: none). */
+void gt_write_psl_ex(FILE *f, const gt_chains *c, int64_t i, const int64_t counts[4], int basic,
+                     int ins_ne, char t_strand);
 
 /* An axt record's header for gt_put_psl_align: the strand character, the
  * names as they stand in the text, the sizes, and the coordinates as axtRead

@@ -23,6 +23,8 @@ pslFromAlign's column loop (psl.c:1716)      Engine.axt_psl(t_rows, q_rows)
                                              axt_psl_host(...): the same on host threads
 axtScoreSym, default scheme (axt.c:196)      Engine.axt_score(t_rows, q_rows)
                                              axt_score_host(...): the same on host threads
+axtScoreSym, any scheme (lavToAxt -dropSelf) Engine.axt_pair_counts(cs, pieces): letter-pair counts a piece
+                                             axt_pair_counts_host(...): the same from two .2bit files
 axtScoreUngapped per block (axt.c:186-194)   Engine.score_blocks / score_text_blocks (caller text)
 cBlockFindCrossover (chainConnect.c:61-105)  Engine.crossovers / text_crossovers (caller text)
 chainBlocks' kd-tree DP (chainBlock.c:400)   Engine.chain_dp_blocks (total, predecessor per block)
@@ -376,6 +378,24 @@ class Engine:
         check(fn(
             self.h, cs.handle, C.c_void_p(d_pieces), n, C.c_void_p(d_score), C.c_void_p(d_match),
             C.c_void_p(d_ali), C.c_void_p(d_sym), C.c_void_p(stream) if stream else None))
+
+    def axt_pair_counts(self, cs: "ChainSet", pieces: np.ndarray):
+        """(pairs int64 [n, 16], n_cols int64 [n]) of every piece
+        (gac_axt_pair_counts): pairs[p, q * 4 + t] = ungapped columns with query
+        letter q over target letter t (A, C, G, T as read_score_scheme's
+        matrix), n_cols[p] = those with an N on either side."""
+        w = np.ascontiguousarray(np.asarray(pieces, dtype=np.int32).reshape(-1, 5))
+        n = w.shape[0]
+        pairs = np.zeros((n, 16), np.int64)
+        n_cols = np.zeros(n, np.int64)
+        check(lib().gac_axt_pair_counts(self.h, cs.handle, _p(w), n, _p(pairs), _p(n_cols)))
+        return pairs, n_cols
+
+    def axt_pair_counts_device(self, cs: "ChainSet", d_pieces: int, n: int, d_pairs: int,
+                               d_n_cols: int, stream: int = 0) -> None:
+        check(lib().gac_axt_pair_counts_device(
+            self.h, cs.handle, C.c_void_p(d_pieces), n, C.c_void_p(d_pairs), C.c_void_p(d_n_cols),
+            C.c_void_p(stream) if stream else None))
 
     def axt_render(self, cs: "ChainSet", pieces: np.ndarray, offsets=None, out=None,
                    sym=None, clip: bool = False) -> np.ndarray:
@@ -813,6 +833,21 @@ def axt_score_host(t_rows, q_rows, nthreads: int = 0):
     return score, _axt_score_stats(st)
 
 
+def axt_pair_counts_host(t_2bit: str, q_2bit: str, t_seq, q_seq, q_strand, blk_off, blk_t, blk_q,
+                         blk_size, pieces):
+    """Engine.axt_pair_counts' result base by base on the host
+    (gac_axt_pair_counts_host; no device): the sequences come from the two
+    .2bit files, t_seq / q_seq numbering them in file order."""
+    d, _arrs = Engine._desc(t_seq, q_seq, q_strand, blk_off, blk_t, blk_q, blk_size)
+    w = np.ascontiguousarray(np.asarray(pieces, dtype=np.int32).reshape(-1, 5))
+    n = w.shape[0]
+    pairs = np.zeros((n, 16), np.int64)
+    n_cols = np.zeros(n, np.int64)
+    check(lib().gac_axt_pair_counts_host(t_2bit.encode(), q_2bit.encode(), C.byref(d), _p(w), n,
+                                         _p(pairs), _p(n_cols)))
+    return pairs, n_cols
+
+
 def antirepeat_pass(score: float, match, rep: int, total: int, min_score: int = 5000) -> bool:
     """chainAntiRepeat's keep/drop decision for one chain from its composition
     (gac_antirepeat_pass: degeneracyFilter then repeatFilter; host only)."""
@@ -834,4 +869,5 @@ def twobit_mask_runs(path: str, name: str) -> Tuple[np.ndarray, np.ndarray]:
 
 __all__ = ["Engine", "ChainSet", "GapCosts", "read_score_scheme", "GAC_T", "GAC_Q",
            "antirepeat_pass", "twobit_mask_runs", "depth_count_host", "prenet_keep_host",
-           "axt_filter_host", "axt_psl_host", "AXT_PSL_ENTRY", "axt_score_host"]
+           "axt_filter_host", "axt_psl_host", "AXT_PSL_ENTRY", "axt_score_host",
+           "axt_pair_counts_host"]

@@ -72,8 +72,9 @@ extern "C" {
  * 6 = gac_prenet_keep and gac_prenet_keep_host (chainPreNet).
  * 7 = gac_axt_filter and gac_axt_filter_host (filterAxtIdentityEntropy.py).
  * 8 = gac_axt_psl, gac_axt_psl_host and gac_axtpsl_free (axtToPsl).
- * 9 = gac_axt_score and gac_axt_score_host (axtToMaf -score / -scoreZero). */
-#define GAC_ABI_MINOR 9
+ * 9 = gac_axt_score and gac_axt_score_host (axtToMaf -score / -scoreZero).
+ * 10 = gac_axt_pair_counts[_device] and gac_axt_pair_counts_host (lavToAxt -dropSelf). */
+#define GAC_ABI_MINOR 10
 
 /* return codes */
 #define GAC_OK 0
@@ -658,6 +659,26 @@ int gac_axt_measure(gac_ctx *ctx, const gac_chainset *cs, const gac_window *piec
 int gac_axt_measure_device(gac_ctx *ctx, const gac_chainset *cs, const gac_window *d_pieces,
                            int64_t n, int32_t *d_score, int64_t *d_match, int64_t *d_ali,
                            int64_t *d_sym, void *stream);
+/* Per piece, what axtScoreSym (axt.c:196-229) needs of the letters to score
+ * the piece under ANY matrix (lavToAxt -dropSelf rescores with -scoreScheme):
+ *   pairs[p * 16 + q * 4 + t] = columns without a dash whose query letter is q
+ *              and target letter t, A,C,G,T order as gac_scheme_read,
+ *              case-blind, '-' pieces on the reverse complement
+ *   n_cols[p] = columns without a dash with an N on either side (they score 0)
+ * so that sum(pairs[p]) + n_cols[p] is gac_axt_measure's ali[p], and the
+ * default matrix over pairs[p] minus the gap terms its score[p].  The gap terms
+ * need no sequence and are the caller's.  t_start / t_end are not read.
+ * Arguments, state and errors as gac_axt_measure; n == 0 writes nothing. */
+int gac_axt_pair_counts(gac_ctx *ctx, const gac_chainset *cs, const gac_window *pieces, int64_t n,
+                        int64_t *pairs, int64_t *n_cols);
+int gac_axt_pair_counts_device(gac_ctx *ctx, const gac_chainset *cs, const gac_window *d_pieces,
+                               int64_t n, int64_t *d_pairs, int64_t *d_n_cols, void *stream);
+/* The same on the host, no device: the sequences read from two .2bit files,
+ * d->t_seq / d->q_seq numbering the files' sequences in file order.  A block
+ * outside its sequence, a window outside its chain and a negative or
+ * double-sided gap inside a piece are GAC_E_ARG. */
+int gac_axt_pair_counts_host(const char *t_2bit, const char *q_2bit, const gac_chainset_desc *d,
+                             const gac_window *pieces, int64_t n, int64_t *pairs, int64_t *n_cols);
 /* The rows of every piece as axtFromBlocks fills them (chainToAxt.c:58-86)
  * from twoBitReadSeqFragExt(doMask=TRUE) text (chainToAxt/chainToAxt.c:48-67:
  * 'ACGTN', lower case in mask runs, '-' chains reverse-complemented with case
